@@ -20,6 +20,14 @@ Weak scaling: per-GPU work is fixed (``--videos-per-step`` per rank);
 Other BASELINE configs: ``--model i3d_raft`` (config 4; ``--flow pwc``
 for the PWC variant), ``--model resnet50`` (config 3), ``--model
 vggish_r21d`` (config 5).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON
+line; ``ms_per_step`` is the wall time of one timed step.  ``--dump-outputs
+DIR`` additionally writes the feature array the last timed step returned to
+``DIR/features.npy`` (float32) — inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.  ``--full``
+is where any measurement beyond the headline figure belongs (baselines,
+other precisions, per-kernel runs); none exists yet, so it changes nothing.
 """
 from __future__ import annotations
 
@@ -175,8 +183,9 @@ def bench_clip(args, device, dtype, rank, world):
             step()
         sync(device, world)
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            step()
+            last = step()
         sync(device, world)
         dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, device, world)
@@ -186,6 +195,7 @@ def bench_clip(args, device, dtype, rank, world):
         'value': total_frames / dt,
         'unit': 'frames/sec',
         'ms_per_step': dt / args.steps * 1000.0,
+        'outputs': {'features': last},
         'config': {'model': 'CLIP-ViT-B/32', 'global_batch': videos * world,
                    'seq_len': frames_per_video, 'resolution': 224,
                    'parallelism': f'dp{world}'},
@@ -289,8 +299,9 @@ def bench_i3d_raft(args, device, dtype, rank, world):
             step()
         sync(device, world)
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            step()
+            last = step()
         sync(device, world)
         dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, device, world)
@@ -300,6 +311,7 @@ def bench_i3d_raft(args, device, dtype, rank, world):
         'value': total_clips / dt,
         'unit': 'clips/sec',
         'ms_per_step': dt / args.steps * 1000.0,
+        'outputs': {'features': last},
         'config': {'model': f'I3D+{args.flow.upper()}',
                    'global_batch': clips * world,
                    'seq_len': stack, 'resolution': 224,
@@ -410,8 +422,9 @@ def bench_resnet(args, device, dtype, rank, world):
             step()
         sync(device, world)
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            step()
+            last = step()
         sync(device, world)
         dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, device, world)
@@ -421,6 +434,7 @@ def bench_resnet(args, device, dtype, rank, world):
         'value': total / dt,
         'unit': 'frames/sec',
         'ms_per_step': dt / args.steps * 1000.0,
+        'outputs': {'features': last},
         'config': {'model': 'ResNet-50', 'global_batch': n_frames * world,
                    'seq_len': 1, 'resolution': 224,
                    'parallelism': f'dp{world}'},
@@ -468,8 +482,9 @@ def bench_vggish_r21d(args, device, dtype, rank, world):
             step()
         sync(device, world)
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            step()
+            last = step()
         sync(device, world)
         dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, device, world)
@@ -479,11 +494,33 @@ def bench_vggish_r21d(args, device, dtype, rank, world):
         'value': total / dt,
         'unit': 'clips/sec',
         'ms_per_step': dt / args.steps * 1000.0,
+        'outputs': {'features': last},
         'config': {'model': f'VGGish+R(2+1)D-{args.r21d_depth}',
                    'global_batch': clips * world,
                    'seq_len': 16, 'resolution': 112,
                    'parallelism': f'dp{world}'},
     }
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """Write what the last timed step returned as ``out_dir/<name>.npy``
+    (float32).  An array over its share of the 64 MB budget is stored as a
+    fixed, seeded sample of its flattened elements, so two builds run with
+    the same arguments still compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        a = t.detach().to('cpu', torch.float32).numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.random.default_rng(0).choice(a.size, keep, replace=False)
+            idx.sort()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
 
 
 def main():
@@ -516,6 +553,13 @@ def main():
     p.add_argument('--dtype', choices=['bf16', 'fp32'], default=None)
     p.add_argument('--no-graphs', action='store_true',
                    help='disable hipGraph capture of the forward')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write the arrays the last '
+                        'timed step returned as DIR/<name>.npy (float32)')
+    p.add_argument('--full', action='store_true',
+                   help='also run every measurement beyond the headline '
+                        'figure; a plain run already times only the selected '
+                        'config, so there is nothing extra to run yet')
     args = p.parse_args()
 
     if args.clips_per_step is None:
@@ -539,6 +583,8 @@ def main():
     res = bench_fns[args.model](args, device, dtype, rank, world)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res['outputs'])
         out = {
             'metric': res['metric'],
             'value': round(res['value'], 2),
