@@ -27,6 +27,9 @@ SHAPES = [
     (8192, 8192, 8192, 'none', 'ladder 8192^3'),
     (19200, 3072, 768, 'quick_gelu', 'CLIP fc1 (fb384)'),
     (19200, 2304, 768, 'none', 'CLIP qkv (fb384)'),
+    # fc1's shape without the activation: the difference to the fc1 row is
+    # the cost of the fused QuickGELU epilogue
+    (19200, 3072, 768, 'none', 'CLIP fc1-noact (fb384)'),
     (1204224, 64, 64, 'relu', 'rn50 l1 conv1 (thin)'),
     (1204224, 256, 64, 'relu', 'rn50 l1 conv3 (thin)'),
     (1204224, 128, 256, 'relu', 'rn50 l2 conv1 (thin)'),
@@ -46,7 +49,12 @@ def timeit(fn, iters=50):
     return (time.perf_counter() - t0) / iters
 
 
+# VFA_GEMM_ONLY=substring: run only the rows whose label contains it
+ONLY = os.environ.get('VFA_GEMM_ONLY', '')
+
 for m, n, k, act, label in SHAPES:
+    if ONLY and ONLY not in label:
+        continue
     torch.manual_seed(0)
     # VFA_GEMM_COLD=N: rotate N input buffers so A can't stay resident in
     # the 256 MiB Infinity Cache between iterations (in-model conditions —

@@ -60,10 +60,11 @@ class MLP(nn.Module):
         self.c_proj = nn.Linear(4 * width, width)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        # fc1 + QuickGELU fused into one MFMA GEMM epilogue on GPU (wins at
-        # K=768: 528 vs 358 TF measured incl. the saved act round trip);
-        # fc2 stays on hipBLASLt, which wins at K=3072 (919 vs 660 TF) —
-        # see gpurun_out/bench_gemm.log
+        # fc1 + QuickGELU fused into one MFMA GEMM epilogue on GPU (the
+        # persistent 256^2 kernel of gemm.hip: 766-793 TF vs 363 TF for
+        # hipBLASLt + a separate activation pass at the 384-frame chunk
+        # shape, profiles/clip_fc1_epilogue.md); fc2 stays on hipBLASLt,
+        # which wins at K=3072 (919 vs 660 TF)
         h = ops.linear_act(x, self.c_fc.weight, self.c_fc.bias, 'quick_gelu')
         return self.c_proj(h)
 

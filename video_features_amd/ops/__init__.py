@@ -404,6 +404,8 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor,
         return y * torch.sigmoid(1.702 * y)
     if act == 'gelu':
         return torch.nn.functional.gelu(y, approximate='tanh')
+    if act == 'leaky_relu':
+        return torch.nn.functional.leaky_relu(y, 0.1)
     return y
 
 

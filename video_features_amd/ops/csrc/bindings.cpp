@@ -399,6 +399,8 @@ torch::Tensor linear_act(torch::Tensor x, torch::Tensor w,
   // ragged M/N/K handled by the guarded staging path; K%8 keeps the
   // 16-B row segments aligned
   TORCH_CHECK(w.size(1) == kk && kk % 8 == 0, "K%8==0 required");
+  TORCH_CHECK(act >= 0 && act <= 4, "linear_act: unknown activation id ",
+              act);
   const void* bptr = nullptr;
   torch::Tensor bc;
   if (bias.has_value()) {

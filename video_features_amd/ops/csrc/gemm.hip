@@ -1,9 +1,20 @@
 // Fused MFMA linear kernel for gfx950:  C = act(A @ W^T + bias), bf16.
 //
 //   A (M, K) row-major, W (N, K) row-major (torch nn.Linear layout), both
-//   bf16; C (M, N) bf16; f32 accumulation; bias + activation applied in
-//   the epilogue (QuickGELU / tanh-GELU / ReLU / none) — the separate
-//   activation kernel's full HBM round trip disappears.
+//   bf16; C (M, N) bf16; f32 accumulation; bias + residual + activation
+//   applied in the epilogue (QuickGELU / tanh-GELU / ReLU / LeakyReLU(0.1)
+//   / none) — the separate activation kernel's full HBM round trip
+//   disappears.
+//
+// Kernels, in routing order (launch_linear):
+//   linear_thin_kernel  M-huge / K-shallow streaming (W resident in LDS)
+//   linear256p_kernel   256x256 full tiles, >= 150 of them: persistent
+//                       tile walk, K pipeline continuous across tiles,
+//                       shared vectorised epilogue (epilogue_strips)
+//   linear8p_kernel     256x256 full tiles, 8-phase pipeline, same
+//                       epilogue; act-none problems of 64..149 tiles
+//   linear_act_kernel   everything else: 128x128 tiles, and the guarded
+//                       256x256 tiles (ragged N column, ragged K)
 //
 // Structure (cdna_hip_programming.md §5): BIG tiles 256x256 (8 waves as
 // 2M x 4N, 128x64 C per wave, 128 KiB LDS) for the transformer shapes,
@@ -19,6 +30,7 @@
 // with an identical LDS image.
 #include "vfa_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -40,14 +52,90 @@ __device__ __forceinline__ int swz(int byte_off) {
   return byte_off ^ (((byte_off >> 8) & 7) << 4);
 }
 
+// act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
 __device__ __forceinline__ float act_f(float x, int kind) {
   if (kind == 1) return fmaxf(x, 0.f);
-  if (kind == 2) return x / (1.0f + __expf(-1.702f * x));   // QuickGELU
+  if (kind == 2) {
+    // QuickGELU x*sigmoid(1.702x) as x * rcp(1 + exp2(c*x)), c folded:
+    // one v_exp_f32 + one v_rcp_f32 + 3 VALU, where the IEEE division of
+    // x / (1 + __expf(..)) cost ~25 instructions per element.  Both
+    // approximations are ~1 ulp in f32, far below the bf16 output step.
+    const float c = -1.702f * 1.4426950408889634f;
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(c * x));
+  }
   if (kind == 3) {
     const float k0 = 0.7978845608028654f, k1 = 0.044715f;
     return 0.5f * x * (1.0f + tanhf(k0 * (x + k1 * x * x * x)));
   }
+  if (kind == 4) return x > 0.f ? x : 0.1f * x;
   return x;
+}
+
+// Shared full-tile epilogue of the two 256x256 kernels: one wave's 128x64
+// f32 accumulator block (8x4 MFMA tiles) -> bias + residual + activation
+// in f32 -> bf16, stored as row-contiguous 16-B vectors.
+//
+// The MFMA fragment layout gives a lane 4 rows x 1 column per tile, i.e.
+// 2-byte stores where 16 lanes cover 32 contiguous bytes.  Each 16x64
+// strip is instead bounced through a wave-private 4 KiB f32 LDS tile `ep`
+// and read back as (row, 8 columns) per lane, so bias / residual / output
+// are 16-B accesses on 128-B-contiguous rows and the arithmetic stays in
+// f32 up to the single bf16 rounding.  The tile is [16][64] f32 with the
+// 16-column group XORed by (row>>2)&3: the four hi4 lane groups of a
+// fragment write then hit disjoint bank groups, and the read side's 8-col
+// segments stay inside one group.  Wave-local only (lgkmcnt waits, no
+// barrier), so it can run while another tile's glds is in flight.
+template <int ACT, bool HAS_RES>
+__device__ __forceinline__ void epilogue_strips(
+    const f32x4 (&acc)[8][4], float* ep, const __bf16* __restrict__ bias,
+    const __bf16* __restrict__ res, __bf16* __restrict__ c, int n,
+    long long row0, int col0, int lane) {
+  const int lo = lane & 15, hi4 = lane >> 4;
+  const int ec = (lane & 7) * 8;
+  const int col = col0 + ec;
+  float bf[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) bf[e] = 0.f;
+  if (bias) {
+    const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(bias + col);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bf[e] = (float)b8[e];
+  }
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) {
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        ep[(hi4 * 4 + r) * 64 + (((jj ^ hi4) << 4) | lo)] = acc[mi][jj][r];
+    __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0), wave-local tile
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int er = p * 8 + (lane >> 3);
+      const float* src = ep + er * 64 + (ec ^ (((er >> 2) & 3) << 4));
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(src);
+      const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 4);
+      const long long o = (row0 + mi * 16 + er) * n + col;
+      bf16x8 rr8{};
+      if (HAS_RES) rr8 = *reinterpret_cast<const bf16x8*>(res + o);
+      bf16x8 o8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float v = (e < 4 ? v0[e & 3] : v1[e & 3]) + bf[e];
+        if (HAS_RES) v += (float)rr8[e];
+        o8[e] = (__bf16)act_f(v, ACT);
+      }
+      *reinterpret_cast<bf16x8*>(c + o) = o8;
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);      // reads done before reuse
+  }
+}
+
+// XCD-aware bijective remap (consecutive remapped ids share an XCD)
+__device__ __forceinline__ int xcd_remap(int wg, int nwg) {
+  const int xcd = wg % 8, orig = wg / 8;
+  const int q = nwg / 8, r = nwg % 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig;
 }
 
 // stage a (ROWS x 64) bf16 tile into a swizzled LDS image (see swz())
@@ -98,18 +186,21 @@ __device__ __forceinline__ void stage_guard(const __bf16* __restrict__ g,
                                             char* lds_base, int tid) {
   for (int t = tid; t < ROWS * 8; t += THREADS) {   // 8 16-B segs per row
     const int row = t >> 3, seg = t & 7;
-    uint4 v = {0u, 0u, 0u, 0u};
+    bf16x8 v{};
     if (row < valid_rows && seg * 8 < valid_k) {
       if ((seg + 1) * 8 <= valid_k) {
-        v = *reinterpret_cast<const uint4*>(g + row * row_stride_elems +
-                                            seg * 8);
+        v = *reinterpret_cast<const bf16x8*>(g + row * row_stride_elems +
+                                             seg * 8);
       } else {
-        __bf16* e = reinterpret_cast<__bf16*>(&v);
-        for (int j = 0; seg * 8 + j < valid_k; ++j)
-          e[j] = g[row * row_stride_elems + seg * 8 + j];
+        // compile-time element index: a runtime-indexed local goes to
+        // scratch
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (seg * 8 + j < valid_k)
+            v[j] = g[row * row_stride_elems + seg * 8 + j];
       }
     }
-    *reinterpret_cast<uint4*>(lds_base + swz(row * 128 + seg * 16)) = v;
+    *reinterpret_cast<bf16x8*>(lds_base + swz(row * 128 + seg * 16)) = v;
   }
 }
 
@@ -122,7 +213,7 @@ void linear_act_kernel(const __bf16* __restrict__ a,
                        const __bf16* __restrict__ bias,
                        const __bf16* __restrict__ res,
                        __bf16* __restrict__ c, int m, int n, int k,
-                       int tiles_m, int tiles_n) {
+                       int tiles_m, int tile_base) {
   constexpr int BM = BIG ? 256 : 128, BN = BIG ? 256 : 128;
   constexpr int WAVES = BIG ? 8 : 4;
   constexpr int WN = BIG ? 4 : 2;              // waves along N
@@ -137,14 +228,10 @@ void linear_act_kernel(const __bf16* __restrict__ a,
     return smem + buf * (TILE_A + TILE_BB) + TILE_A;
   };
 
-  // XCD-aware bijective remap (consecutive remapped ids share an XCD)
-  const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int xcd = wg % 8, orig = wg / 8;
-    const int q = nwg / 8, r = nwg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig;
-  }
+  // the grid covers tiles tile_base .. tile_base + gridDim.x (tile id =
+  // tile_n * tiles_m + tile_m); tile_base > 0 when the interior tiles of
+  // the problem went to linear256p_kernel and only the edge column is here
+  const int wg = tile_base + xcd_remap(blockIdx.x, gridDim.x);
   const int tile_n = wg / tiles_m, tile_m = wg % tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -226,23 +313,157 @@ void linear_act_kernel(const __bf16* __restrict__ a,
     // drains the in-flight glds and orders reads before buffer reuse
   }
 
-  // epilogue: bias + activation, bf16 store (bounds only on edge tiles)
+  // epilogue: bias + residual + activation, bf16 store in the fragment
+  // layout.  The bounds guards and the residual test are hoisted: four
+  // specialisations picked by two block-uniform branches, so interior
+  // tiles run no per-element compare and edge tiles no per-element
+  // null test.  (The 256^2 hot path is linear256p_kernel's epilogue; this
+  // one serves the small tile and the edge / ragged-K tiles.)
+  auto epilogue = [&](auto guarded, auto has_res) {
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int col = n0 + wn * (NJ * 16) + j * 16 + lo;
-    if (!tile_full && col >= n) continue;
-    const float bv = bias ? (float)bias[col] : 0.f;
+    for (int j = 0; j < NJ; ++j) {
+      const int col = n0 + wn * (NJ * 16) + j * 16 + lo;
+      if (guarded.value && col >= n) continue;
+      const float bv = bias ? (float)bias[col] : 0.f;
 #pragma unroll
-    for (int i = 0; i < MI; ++i) {
+      for (int i = 0; i < MI; ++i) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * (MI * 16) + i * 16 + hi4 * 4 + r;
-        if (!tile_full && row >= m) continue;
-        float v = acc[i][j][r] + bv;
-        if (res) v += (float)res[(long long)row * n + col];
-        c[(long long)row * n + col] = (__bf16)act_f(v, ACT);
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + wm * (MI * 16) + i * 16 + hi4 * 4 + r;
+          if (guarded.value && row >= m) continue;
+          float v = acc[i][j][r] + bv;
+          if (has_res.value && (!BIG || res))
+            v += (float)res[(long long)row * n + col];
+          c[(long long)row * n + col] = (__bf16)act_f(v, ACT);
+        }
       }
     }
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (BIG) {
+    // edge column / ragged-K tiles only, at 256 VGPRs: splitting on the
+    // residual as well spills 8-12 registers, so that test stays inside
+    if (tile_full) epilogue(F{}, T{}); else epilogue(T{}, T{});
+  } else if (tile_full) {
+    if (res) epilogue(F{}, T{}); else epilogue(F{}, F{});
+  } else {
+    if (res) epilogue(T{}, T{}); else epilogue(T{}, F{});
+  }
+}
+
+// ------------------------------------------------- persistent 256^2 tiles
+// The full-tile (m0+256 <= m, n0+256 <= n, k % 64 == 0) hot path of the
+// 2-buffer kernel above, as a persistent loop: min(tiles, CUs) blocks, each
+// walking tiles blockIdx.x, +gridDim.x, ... through the XCD remap.  Same
+// staging, swizzle and MFMA schedule; what changes is the tile boundary:
+//  - the K pipeline never stops.  Buffer parity runs over a counter that
+//    continues across tiles, so in a tile's LAST K-step the "next K-tile"
+//    glds are simply the next tile's K-tile 0 (into the buffer every wave
+//    left at the previous barrier — the same ordering argument as inside
+//    a tile).  The first-load latency of tile t+1 is hidden behind tile
+//    t's last MFMAs and its epilogue instead of being exposed per tile;
+//  - the epilogue (epilogue_strips) bounces through its own 32 KiB LDS
+//    region beside the 128 KiB of staging, wave-local, no barrier — so it
+//    neither touches the buffers the prefetch is landing in nor drains it.
+//    The next tile's first __syncthreads() does the vmcnt(0) drain.
+// No grid-wide synchronisation: blocks are independent, co-residency is
+// not assumed, graph capture is unaffected.
+template <int ACT>
+__global__ __launch_bounds__(512, 1)
+void linear256p_kernel(const __bf16* __restrict__ a,
+                       const __bf16* __restrict__ w,
+                       const __bf16* __restrict__ bias,
+                       const __bf16* __restrict__ res,
+                       __bf16* __restrict__ c, int n, int k, int tiles_m,
+                       int ntiles) {
+  constexpr int TILE = 256 * BK * 2;           // one operand, one K-tile
+  extern __shared__ __attribute__((aligned(1024))) char smem_p[];
+  auto sA = [&](int buf) { return smem_p + buf * (2 * TILE); };
+  auto sB = [&](int buf) { return smem_p + buf * (2 * TILE) + TILE; };
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lo = lane & 15, hi4 = lane >> 4;
+  const int wm = wave >> 2, wn = wave & 3;
+  float* ep = reinterpret_cast<float*>(smem_p + 4 * TILE) + wave * (16 * 64);
+
+  const int nk = k / BK;
+  int v = blockIdx.x;                          // virtual block id
+  int wg = xcd_remap(v, ntiles);
+  int m0 = (wg % tiles_m) * 256, n0 = (wg / tiles_m) * 256;
+  const __bf16* ap = a + (long long)m0 * k;
+  const __bf16* wp = w + (long long)n0 * k;
+
+  stage_glds<256, 8>(ap, k, sA(0), wave, lane);
+  stage_glds<256, 8>(wp, k, sB(0), wave, lane);
+
+  int it = 0;                                  // K-steps done, all tiles
+  for (;;) {
+    const int vn = v + gridDim.x;
+    const bool more = vn < ntiles;
+    int m0n = m0, n0n = n0;
+    if (more) {
+      const int wgn = xcd_remap(vn, ntiles);
+      m0n = (wgn % tiles_m) * 256;
+      n0n = (wgn / tiles_m) * 256;
+    }
+    const __bf16* apn = a + (long long)m0n * k;
+    const __bf16* wpn = w + (long long)n0n * k;
+
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kt = 0; kt < nk; ++kt, ++it) {
+      __syncthreads();                         // K-tile resident, drained
+      const int cur = it & 1;
+      const bool last = kt + 1 == nk;
+      // what the other buffer gets: this tile's next K-tile, or — in the
+      // last K-step — the next tile's first
+      const __bf16* an = last ? apn : ap + (long long)(kt + 1) * BK;
+      const __bf16* wn_ = last ? wpn : wp + (long long)(kt + 1) * BK;
+      const bool issue = !last || more;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {         // two 32-deep MFMA steps
+        bf16x8 afr[8], bfr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int brow = wn * 64 + j * 16 + lo;
+          bfr[j] = *reinterpret_cast<const bf16x8*>(
+              sB(cur) + swz(brow * 128 + kk * 64 + hi4 * 16));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int arow = wm * 128 + i * 16 + lo;
+          afr[i] = *reinterpret_cast<const bf16x8*>(
+              sA(cur) + swz(arow * 128 + kk * 64 + hi4 * 16));
+        }
+        if (issue) {
+          stage_glds_piece<256, 8>(an, k, sA(1 - cur), wave, lane, kk, 2);
+          stage_glds_piece<256, 8>(wn_, k, sB(1 - cur), wave, lane, kk, 2);
+        }
+        __builtin_amdgcn_s_setprio(1);   // keep the MFMA cluster issuing
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afr[i], bfr[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+      }
+    }
+
+    const long long row0 = m0 + wm * 128;
+    const int col0 = n0 + wn * 64;
+    if (res)
+      epilogue_strips<ACT, true>(acc, ep, bias, res, c, n, row0, col0, lane);
+    else
+      epilogue_strips<ACT, false>(acc, ep, bias, res, c, n, row0, col0,
+                                  lane);
+    if (!more) break;
+    v = vn; m0 = m0n; n0 = n0n; ap = apn; wp = wpn;
   }
 }
 
@@ -276,13 +497,7 @@ void linear8p_kernel(const __bf16* __restrict__ a,
   extern __shared__ __attribute__((aligned(1024))) char smem8[];
   const int nk = k >> 6;
 
-  const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int xcd = wg % 8, orig = wg / 8;
-    const int q = nwg / 8, r = nwg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig;
-  }
+  const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   const int tile_n = wg / tiles_m, tile_m = wg % tiles_m;
   const int m0 = tile_m * 256, n0 = tile_n * 256;
 
@@ -394,40 +609,16 @@ void linear8p_kernel(const __bf16* __restrict__ a,
     }
   }
 
-  // epilogue: LDS-bounce to 16-B vectorized bias/res/store (full tiles,
-  // no guards).  __syncthreads drains the dummy glds still in flight.
+  // epilogue: the shared f32 LDS bounce (epilogue_strips), here inside the
+  // dead staging rings.  __syncthreads drains the dummy glds in flight.
   __syncthreads();
-  __bf16* ep = reinterpret_cast<__bf16*>(smem8) + wave * (16 * 72);
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) {
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        ep[(hi4 * 4 + r) * 72 + jj * 16 + lo] = (__bf16)acc[mi][jj][r];
-    __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0), wave-local tile
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int er = p * 8 + (lane >> 3);
-      const int ec = (lane & 7) * 8;
-      const long long row = m0 + wm * 128 + mi * 16 + er;
-      const int col = n0 + wn * 64 + ec;
-      bf16x8 v8 = *reinterpret_cast<const bf16x8*>(ep + er * 72 + ec);
-      bf16x8 o8;
-      bf16x8 b8{}, rr8{};
-      if (bias) b8 = *reinterpret_cast<const bf16x8*>(bias + col);
-      if (res) rr8 = *reinterpret_cast<const bf16x8*>(res + row * n + col);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = (float)v8[e];
-        if (bias) v += (float)b8[e];
-        if (res) v += (float)rr8[e];
-        o8[e] = (__bf16)act_f(v, ACT);
-      }
-      *reinterpret_cast<bf16x8*>(c + row * n + col) = o8;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);      // reads done before reuse
-  }
+  float* ep = reinterpret_cast<float*>(smem8) + wave * (16 * 64);
+  const long long row0 = m0 + wm * 128;
+  const int col0 = n0 + wn * 64;
+  if (res)
+    epilogue_strips<ACT, true>(acc, ep, bias, res, c, n, row0, col0, lane);
+  else
+    epilogue_strips<ACT, false>(acc, ep, bias, res, c, n, row0, col0, lane);
 }
 
 template <int ACT>
@@ -437,7 +628,7 @@ bool launch_8p(const void* a, const void* w, const void* bias,
   if (m % 256 || n % 256 || k % 64 || k / 64 < 3) return false;
   const long long tiles = (long long)(m / 256) * (n / 256);
   if (tiles < 64) return false;              // chip fill
-  static bool attr_set[4] = {};
+  static bool attr_set[5] = {};
   if (!attr_set[ACT]) {
     (void)hipFuncSetAttribute(
         reinterpret_cast<const void*>(&linear8p_kernel<ACT>),
@@ -643,21 +834,50 @@ void launch_tile(const void* a, const void* w, const void* bias,
                  hipStream_t stream) {
   constexpr int BM = BIG ? 256 : 128, BN = BIG ? 256 : 128;
   const int tiles_m = (m + BM - 1) / BM, tiles_n = (n + BN - 1) / BN;
-  const dim3 grid(tiles_m * tiles_n);
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
   const bool full = (k % BK == 0);   // per-tile M/N edges handled inside
+  int tile_base = 0;
+  if (BIG && full && m % 256 == 0 && n >= 256 && n % 8 == 0) {
+    // interior tile columns -> the persistent kernel; what is left for
+    // the guarded kernel below is at most the ragged last column
+    // (n % 8: its 16-B bias/res/out vectors need 8-element row alignment)
+    static const int ncu = [] {
+      int dev = 0, v = 0;
+      (void)hipGetDevice(&dev);
+      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                                  dev);
+      return v > 0 ? v : 256;
+    }();
+    constexpr size_t lds_p = 160 * 1024;       // 128 staging + 32 bounce
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&linear256p_kernel<ACT>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
+      attr_set = true;
+    }
+    const int ntiles = tiles_m * (n / 256);
+    hipLaunchKernelGGL((linear256p_kernel<ACT>),
+                       dim3((unsigned)min(ntiles, ncu)), dim3(512), lds_p,
+                       stream, (const __bf16*)a, (const __bf16*)w,
+                       (const __bf16*)bias, (const __bf16*)res, (__bf16*)c,
+                       n, k, tiles_m, ntiles);
+    if (n % 256 == 0) return;
+    tile_base = ntiles;
+  }
+  const dim3 grid(tiles_m * tiles_n - tile_base);
   if (full)
     hipLaunchKernelGGL((linear_act_kernel<ACT, true, BIG>), grid,
                        dim3(BIG ? 512 : 256), lds, stream, (const __bf16*)a,
                        (const __bf16*)w, (const __bf16*)bias,
                        (const __bf16*)res, (__bf16*)c, m, n, k, tiles_m,
-                       tiles_n);
+                       tile_base);
   else
     hipLaunchKernelGGL((linear_act_kernel<ACT, false, BIG>), grid,
                        dim3(BIG ? 512 : 256), lds, stream, (const __bf16*)a,
                        (const __bf16*)w, (const __bf16*)bias,
                        (const __bf16*)res, (__bf16*)c, m, n, k, tiles_m,
-                       tiles_n);
+                       tile_base);
 }
 
 template <int ACT>
@@ -669,17 +889,24 @@ void launch_linear(const void* a, const void* w, const void* bias,
   // tail tile and the block-round quantization cost more than the smaller
   // tile's overhead — measured 339 vs 528 TF at M=9600) and the grid
   // still fills the chip
-  // 8-phase pipelined kernel: with the conflict-free LDS swizzle it wins
-  // the act-none shapes (qkv 742 vs 714 TF, 8192^3 1160 vs 1104) but
-  // trails the 2-buffer kernel's fused-activation epilogue on fc1 — route
-  // by activation.  VFA_NO_8P / VFA_8P force either way for A/B.
+  // Both 256^2 kernels share one epilogue (epilogue_strips).  With it and
+  // the persistent tile walk the 2-buffer kernel wins every shape it takes
+  // (>= 150 tiles), with or without an activation — us/call, persistent
+  // vs 8-phase, same box: fc1+QuickGELU 19200x3072x768 114-118 vs 125,
+  // the same shape act-none 101 vs 113, qkv 19200x2304x768 83 vs 92,
+  // 4096^3 129 vs 134-137, 8192^3 906 vs 920-928, 4096x4096x12288+relu
+  // 334-337 vs 359 — so it goes first.  The 8-phase kernel keeps the
+  // act-none full-tile problems of 64..149 tiles, which the persistent
+  // route does not take.  VFA_8P forces the 8-phase kernel wherever it
+  // can run, VFA_NO_8P disables it, for A/B.
   static const int env8p = getenv("VFA_8P") ? 1
                            : getenv("VFA_NO_8P") ? -1 : 0;
   if (launch_thin<ACT>(a, w, bias, res, c, m, n, k, stream)) return;
-  const bool want8p = env8p > 0 || (env8p == 0 && ACT == 0);
-  if (want8p && launch_8p<ACT>(a, w, bias, res, c, m, n, k, stream)) return;
   const long long tiles = (long long)((m + 255) / 256) * ((n + 255) / 256);
-  if (n >= 256 && m % 256 == 0 && tiles >= 150)
+  const bool big = n >= 256 && m % 256 == 0 && tiles >= 150;
+  const bool want8p = env8p > 0 || (env8p == 0 && ACT == 0 && !big);
+  if (want8p && launch_8p<ACT>(a, w, bias, res, c, m, n, k, stream)) return;
+  if (big)
     launch_tile<ACT, true>(a, w, bias, res, c, m, n, k, stream);
   else
     launch_tile<ACT, false>(a, w, bias, res, c, m, n, k, stream);
@@ -689,7 +916,7 @@ void launch_linear(const void* a, const void* w, const void* bias,
 
 extern "C" {
 
-// act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh
+// act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
 void vfa_linear_act(const void* a, const void* w, const void* bias,
                     const void* res, void* c, int m, int n, int k, int act,
                     hipStream_t stream) {
@@ -698,6 +925,8 @@ void vfa_linear_act(const void* a, const void* w, const void* bias,
     case 1: launch_linear<1>(a, w, bias, res, c, m, n, k, stream); break;
     case 2: launch_linear<2>(a, w, bias, res, c, m, n, k, stream); break;
     case 3: launch_linear<3>(a, w, bias, res, c, m, n, k, stream); break;
+    case 4: launch_linear<4>(a, w, bias, res, c, m, n, k, stream); break;
+    default: break;                            // rejected by the binding
   }
 }
 
