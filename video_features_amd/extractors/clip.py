@@ -3,7 +3,8 @@
 Capability parity with the reference's ``ExtractCLIP``
 (reference models/CLIP/extract_clip.py): ``uni_N``/``fix_N`` frame sampling,
 feature shape (N, 512), meta keys fps/timestamps_ms, ``external_call`` API,
-feature types CLIP-ViT-B/32, CLIP-ViT-B/16, CLIP4CLIP-ViT-B-32 (the
+feature types CLIP-ViT-B/32, CLIP-ViT-B/16, CLIP4CLIP-ViT-B-32, the ResNet
+towers CLIP-RN50, CLIP-RN101, CLIP-RN50x4, CLIP-RN50x16 (the
 CLIP4CLIP variant loads task-tuned ViT-B/32 weights from ``weights_path``).
 """
 from __future__ import annotations

@@ -45,6 +45,8 @@ _REGISTRY: Dict[str, Callable] = {
     'CLIP4CLIP-ViT-B-32': _clip,
     'CLIP-RN50': _clip,
     'CLIP-RN101': _clip,
+    'CLIP-RN50x4': _clip,
+    'CLIP-RN50x16': _clip,
     'resnet18': _resnet,
     'resnet34': _resnet,
     'resnet50': _resnet,

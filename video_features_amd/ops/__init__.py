@@ -373,6 +373,74 @@ def maxpool2d(x: torch.Tensor, kernel, stride, padding,
                                           padding)
 
 
+def avgpool2d_nhwc(x: torch.Tensor, k: int = 2) -> torch.Tensor:
+    """``nn.AvgPool2d(k)`` (window = stride = k, floor output size) on a
+    channels_last bf16 (B, C, H, W) map — CLIP's ModifiedResNet pools where
+    torchvision's ResNet strides.  HIP path: one memory-bound kernel, 16-B
+    loads over channels, f32 sum, one rounding to bf16; the result is
+    channels_last.  It requires C % 8 == 0 and raises otherwise.  CPU and
+    non-bf16 tensors take ``F.avg_pool2d``."""
+    if _use_hip(x) and x.dtype == torch.bfloat16:
+        if x.shape[1] % 8 != 0:
+            raise ValueError('avgpool2d_nhwc: C % 8 == 0 required on the '
+                             f'HIP path, got C={x.shape[1]}')
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        return _ext.avgpool2d_nhwc(x, int(k))
+    return torch.nn.functional.avg_pool2d(x, k)
+
+
+def attnpool_tokens(x: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """Token matrix of CLIP's ``AttentionPool2d``: ``x`` (B, HW, C) — a free
+    view of the channels_last trunk output — and the learned positional
+    embedding ``pos`` (HW+1, C) give ``t`` (B, HW+1, C) with
+    ``t[:, 0] = mean_j x[:, j] + pos[0]`` (mean in f32) and
+    ``t[:, 1 + j] = x[:, j] + pos[1 + j]``.  HIP path (bf16): one read of
+    ``x``, one write of ``t``, each value rounded once; requires C % 8 == 0
+    and raises otherwise.  CPU and non-bf16 tensors take the torch
+    construction in f32."""
+    if pos.shape != (x.shape[1] + 1, x.shape[2]):
+        raise ValueError(f'attnpool_tokens: pos must be (HW+1, C) = '
+                         f'{(x.shape[1] + 1, x.shape[2])}, got '
+                         f'{tuple(pos.shape)}')
+    if _use_hip(x) and x.dtype == torch.bfloat16:
+        if x.shape[2] % 8 != 0:
+            raise ValueError('attnpool_tokens: C % 8 == 0 required on the '
+                             f'HIP path, got C={x.shape[2]}')
+        return _ext.attnpool_tokens(x.contiguous(),
+                                    pos.to(torch.bfloat16).contiguous())
+    xf = x.float()
+    t = torch.cat([xf.mean(dim=1, keepdim=True), xf], dim=1) + pos.float()
+    return t.to(x.dtype)
+
+
+def attention_pool(q: torch.Tensor, kv: torch.Tensor,
+                   heads: int) -> torch.Tensor:
+    """Single-query multi-head attention, the attention step of CLIP's
+    ``AttentionPool2d``: ``q`` (B, C) is the projection of token 0 only,
+    ``kv`` (B, L, 2C) is packed ``[k | v]`` as one GEMM with the
+    concatenated ``[k_proj; v_proj]`` weight writes it; returns (B, C) with
+    ``o[b, h] = softmax_j(q_h . k_jh / sqrt(d)) . v_jh``, d = C / heads.
+
+    HIP path (bf16, d == 64 — all four CLIP ResNet towers): one wave per
+    (b, h), f32 arithmetic, max-subtracted online softmax over 64-key
+    chunks, any L >= 1.  Any other head dim, dtype, or a CPU tensor takes
+    the torch composition below (f32 math, result in ``q``'s dtype)."""
+    b, c = q.shape
+    l = kv.shape[1]
+    d = c // heads
+    if (_use_hip(q) and q.dtype == torch.bfloat16
+            and kv.dtype == torch.bfloat16 and d == 64 and c == heads * 64):
+        return _ext.attention_pool(q.contiguous(), kv.contiguous(),
+                                   int(heads))
+    qh = q.float().view(b, heads, 1, d)
+    kh = kv[..., :c].float().reshape(b, l, heads, d).permute(0, 2, 1, 3)
+    vh = kv[..., c:].float().reshape(b, l, heads, d).permute(0, 2, 1, 3)
+    attn = (qh @ kh.transpose(-2, -1)) / math.sqrt(d)
+    o = attn.softmax(dim=-1) @ vh                     # (B, H, 1, d)
+    return o.reshape(b, c).to(q.dtype)
+
+
 _ACT_IDS = {'none': 0, 'relu': 1, 'quick_gelu': 2, 'gelu': 3,
             'leaky_relu': 4}
 

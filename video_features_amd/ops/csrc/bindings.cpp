@@ -56,6 +56,12 @@ void vfa_conv2d_nhwc(const void*, const void*, const void*, const void*,
                      int, int, int, int, int, int, int, int, hipStream_t);
 void vfa_pad2d_nhwc(const void*, void*, int, int, int, int, int, int, int,
                     int, int, hipStream_t);
+void vfa_avgpool2d_nhwc(const void*, void*, long long, int, int, int, int,
+                        int, int, hipStream_t);
+void vfa_attnpool_tokens(const void*, const void*, void*, long long, int, int,
+                         hipStream_t);
+void vfa_attention_pool_d64(const void*, const void*, void*, long long, int,
+                            int, float, hipStream_t);
 }
 
 namespace {
@@ -541,6 +547,58 @@ torch::Tensor temporal_merge(torch::Tensor y, int64_t b, int64_t kt,
   return out;
 }
 
+torch::Tensor avgpool2d_nhwc(torch::Tensor x, int64_t k) {
+  // x (B, C, H, W) channels_last bf16 -> (B, C, H/k, W/k) channels_last,
+  // window = stride = k, floor output size (nn.AvgPool2d(k))
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && cl_contig(x),
+              "x must be channels_last");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "avgpool2d_nhwc: bf16");
+  TORCH_CHECK(x.size(1) % 8 == 0, "avgpool2d_nhwc: C % 8 == 0 required");
+  TORCH_CHECK(k >= 1 && k <= x.size(2) && k <= x.size(3),
+              "avgpool2d_nhwc: window larger than the input");
+  const int64_t oh = x.size(2) / k, ow = x.size(3) / k;
+  auto out = torch::empty({x.size(0), oh, ow, x.size(1)}, x.options())
+                 .permute({0, 3, 1, 2});
+  vfa_avgpool2d_nhwc(x.data_ptr(), out.data_ptr(), x.size(0), (int)x.size(1),
+                     (int)x.size(2), (int)x.size(3), (int)oh, (int)ow, (int)k,
+                     current_stream());
+  return out;
+}
+
+torch::Tensor attnpool_tokens(torch::Tensor x, torch::Tensor pos) {
+  // x (B, HW, C) bf16, pos (HW+1, C) bf16 -> t (B, HW+1, C) bf16
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous());
+  TORCH_CHECK(pos.is_cuda() && pos.dim() == 2 && pos.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
+              pos.scalar_type() == torch::kBFloat16, "attnpool_tokens: bf16");
+  const int64_t hw = x.size(1), c = x.size(2);
+  TORCH_CHECK(hw >= 1 && c % 8 == 0, "attnpool_tokens: C % 8 == 0 required");
+  TORCH_CHECK(pos.size(0) == hw + 1 && pos.size(1) == c,
+              "positional embedding must be (HW+1, C)");
+  auto t = torch::empty({x.size(0), hw + 1, c}, x.options());
+  vfa_attnpool_tokens(x.data_ptr(), pos.data_ptr(), t.data_ptr(), x.size(0),
+                      (int)hw, (int)c, current_stream());
+  return t;
+}
+
+torch::Tensor attention_pool(torch::Tensor q, torch::Tensor kv,
+                             int64_t heads) {
+  // q (B, C) bf16, kv (B, L, 2C) bf16 packed [k | v], C == heads * 64
+  TORCH_CHECK(q.is_cuda() && q.dim() == 2 && q.is_contiguous());
+  TORCH_CHECK(kv.is_cuda() && kv.dim() == 3 && kv.is_contiguous());
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+              kv.scalar_type() == torch::kBFloat16, "attention_pool: bf16");
+  const int64_t b = q.size(0), c = q.size(1), l = kv.size(1);
+  TORCH_CHECK(heads >= 1 && c == heads * 64,
+              "attention_pool covers head_dim 64");
+  TORCH_CHECK(kv.size(0) == b && kv.size(2) == 2 * c && l >= 1,
+              "kv must be (B, L>=1, 2C)");
+  auto out = torch::empty({b, c}, q.options());
+  vfa_attention_pool_d64(q.data_ptr(), kv.data_ptr(), out.data_ptr(), b,
+                         (int)heads, (int)l, 0.125f, current_stream());
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -565,5 +623,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_act", &linear_act);
   m.def("conv2d_nhwc", &conv2d_nhwc);
   m.def("temporal_merge", &temporal_merge);
+  m.def("avgpool2d_nhwc", &avgpool2d_nhwc);
+  m.def("attnpool_tokens", &attnpool_tokens);
+  m.def("attention_pool", &attention_pool);
   m.attr("gfx_arch") = "gfx950";
 }

@@ -7,6 +7,9 @@
 // and skips the indices — one dispatch, one read of the tensor.
 // Zero-padding max semantics match F.pad(0) + maxpool exactly: positions
 // outside the input contribute the value 0.
+//
+// Also here: the NHWC bf16 average pool of CLIP's ModifiedResNet
+// (avgpool2d_nhwc, below the max pools).
 #include "vfa_common.h"
 
 namespace {
@@ -98,9 +101,56 @@ __global__ void maxpool2d_same_kernel(const T* __restrict__ x,
   }
 }
 
+// NHWC bf16 average pool, window = stride = k, floor output size
+// (nn.AvgPool2d(k)): CLIP's ModifiedResNet downsamples with this where
+// torchvision's ResNet strides.  One thread per 8 output channels: k*k
+// 16-B loads, f32 sum, one multiply by 1/k^2, ONE rounding to bf16, one
+// 16-B store.  Memory-bound; grid-stride, no LDS.  Requires C % 8 == 0.
+__global__ void avgpool2d_nhwc_kernel(const uint4* __restrict__ x,
+                                      uint4* __restrict__ out, long long n,
+                                      int c8, int ih, int iw, int oh, int ow,
+                                      int k, float inv) {
+  const long long total = n * oh * ow * c8;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int ci = (int)(i % c8);
+    long long r = i / c8;
+    const int xo = (int)(r % ow);
+    r /= ow;
+    const int yo = (int)(r % oh);
+    const long long ni = r / oh;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // (yo*k + dy) <= oh*k - 1 <= ih - 1: the floor keeps windows in-image
+    for (int dy = 0; dy < k; ++dy) {
+      const uint4* row =
+          x + ((ni * ih + (long long)yo * k + dy) * iw + (long long)xo * k) *
+                  c8 + ci;
+      for (int dx = 0; dx < k; ++dx) {
+        float f[8];
+        bf16x8_to_f32(row[(long long)dx * c8], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += f[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] *= inv;
+    out[i] = f32_to_bf16x8(acc);
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+void vfa_avgpool2d_nhwc(const void* x, void* out, long long n, int c, int ih,
+                        int iw, int oh, int ow, int k, hipStream_t stream) {
+  const long long total = n * oh * ow * (c / 8);
+  if (total <= 0) return;
+  const int grid = (int)min((total + 255) / 256, (long long)2048);
+  hipLaunchKernelGGL(avgpool2d_nhwc_kernel, dim3(grid), dim3(256), 0, stream,
+                     (const uint4*)x, (uint4*)out, n, c / 8, ih, iw, oh, ow,
+                     k, 1.f / (float)(k * k));
+}
 
 void vfa_maxpool2d_same(const void* x, void* out, long long n, int c, int ih,
                         int iw, int oh, int ow, int kh, int kw, int sh,

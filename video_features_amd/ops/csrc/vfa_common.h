@@ -46,6 +46,31 @@ __device__ __forceinline__ __half from_f32<__half>(float v) {
   return __float2half(v);
 }
 
+// 8 bf16 in one 16-B vector <-> 8 f32 (memory-bound kernels move bf16 as
+// uint4; the f32 -> bf16 direction rounds to nearest even, NaN kept quiet)
+__device__ __forceinline__ void bf16x8_to_f32(const uint4& v, float* f) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = __uint_as_float(w[j] << 16);
+    f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+  }
+}
+
+__device__ __forceinline__ unsigned f32_to_bf16_bits(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+__device__ __forceinline__ uint4 f32_to_bf16x8(const float* f) {
+  unsigned o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    o[j] = f32_to_bf16_bits(f[2 * j]) | (f32_to_bf16_bits(f[2 * j + 1]) << 16);
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
