@@ -10,12 +10,24 @@ Hot ops (LayerNorm, QuickGELU, the attention core) dispatch through
 ``video_features_amd.ops`` — hand-written CDNA4 HIP kernels on MI355X,
 PyTorch reference implementations on CPU.  Plain GEMMs (qkv/proj/MLP) go to
 rocBLAS/hipBLASLt via ``torch.nn.Linear``.
+
+Only what the output needs is computed.  The [CLS] token, the positional
+embedding and ``ln_pre`` are one kernel (``ops.clip_embed_ln``).  The feature
+is ``ln_post`` of token 0 of the last block, so the last block runs ``ln_1``
+and the K/V projection over all tokens and everything after them — query,
+single-query attention (``ops.attention_pool``), ``proj``, ``ln_2``, the MLP
+and the residual adds — for the [CLS] row of each frame only
+(``VisionTransformer._cls_tail``).  ``VFA_CLIP_FULL_TAIL=1`` runs the last
+block in full instead, for A/B runs and tests; the parameters and
+``state_dict`` keys are the same either way.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from .. import ops
@@ -118,14 +130,15 @@ class VisionTransformer(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(T, 3, R, R) preprocessed frames → (T, output_dim) features."""
         x = self._patch_embed(x)
-        cls = self.class_embedding.to(x.dtype).expand(x.shape[0], 1, -1)
-        x = torch.cat([cls, x], dim=1)
-        x = x + self.positional_embedding.to(x.dtype)
-        x = self.ln_pre(x)
+        # [cls | patches] + positional embedding + ln_pre: one kernel on GPU
+        x = ops.clip_embed_ln(x, self.class_embedding,
+                              self.positional_embedding, self.ln_pre.weight,
+                              self.ln_pre.bias, self.ln_pre.eps)
+        full_tail = ops._env_flag('VFA_CLIP_FULL_TAIL')
         # residual stream carried as (delta, res): every add is fused into
         # the next LayerNorm (ops.layer_norm_residual)
         delta, res = None, x
-        for blk in self.blocks:
+        for blk in (self.blocks if full_tail else self.blocks[:-1]):
             if delta is None:
                 y1, s1 = blk.ln_1(res), res
             else:
@@ -135,9 +148,38 @@ class VisionTransformer(nn.Module):
             y2, s2 = ops.layer_norm_residual(a, s1, blk.ln_2.weight,
                                              blk.ln_2.bias, blk.ln_2.eps)
             delta, res = blk.mlp(y2), s2
-        x = delta + res
-        x = self.ln_post(x[:, 0, :])
+        if full_tail:
+            x = delta + res
+            x = self.ln_post(x[:, 0, :])
+        else:
+            x = self._cls_tail(self.blocks[-1], delta, res)
         return x @ self.proj.to(x.dtype)
+
+    def _cls_tail(self, blk: ResidualAttentionBlock,
+                  delta: Optional[torch.Tensor],
+                  res: torch.Tensor) -> torch.Tensor:
+        """Last block + ``ln_post`` for the [CLS] row alone.  Attention mixes
+        tokens, so ``ln_1`` and the K/V projection still cover every token;
+        the query, ``proj``, ``ln_2``, the MLP and the residual adds are
+        needed for one row per frame.  The weight slices are row views of
+        the block's own parameters."""
+        w = self.cfg.width
+        if delta is None:
+            y1, s1 = blk.ln_1(res), res
+        else:
+            y1, s1 = ops.layer_norm_residual(delta, res, blk.ln_1.weight,
+                                             blk.ln_1.bias, blk.ln_1.eps)
+        qkv = blk.attn.qkv
+        kv = F.linear(y1, qkv.weight[w:], qkv.bias[w:])      # (T, N, 2W)
+        q = F.linear(y1[:, 0], qkv.weight[:w], qkv.bias[:w])  # (T, W)
+        o = ops.attention_pool(q, kv, blk.attn.heads)        # (T, W)
+        a = blk.attn.proj(o)
+        y2, s2 = ops.layer_norm_residual(a, s1[:, 0], blk.ln_2.weight,
+                                         blk.ln_2.bias, blk.ln_2.eps)
+        d = blk.mlp(y2)                                      # M = T
+        y, _ = ops.layer_norm_residual(d, s2, self.ln_post.weight,
+                                       self.ln_post.bias, self.ln_post.eps)
+        return y
 
     # reference parity name (reference extract_clip.py:128 uses
     # model.encode_image)

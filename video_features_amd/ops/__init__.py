@@ -118,6 +118,27 @@ def layer_norm_residual(x: torch.Tensor, res: torch.Tensor,
     return y, s
 
 
+def clip_embed_ln(pe: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor,
+                  weight: torch.Tensor, bias: torch.Tensor,
+                  eps: float = 1e-5) -> torch.Tensor:
+    """CLIP ViT token embedding: ``pe`` (T, P, W) patch embeddings, ``cls``
+    (W), ``pos`` (P+1, W) and the ``ln_pre`` affine give (T, P+1, W) with
+    ``out[t, j] = LN((cls if j == 0 else pe[t, j-1]) + pos[j])``.
+
+    HIP path (W % 8 == 0; bf16, fp16 and fp32 instantiate one template): one
+    kernel reads ``pe`` once and writes the normalised tokens once, sum and
+    statistics in f32, one rounding.  CPU tensors, W % 8 != 0 and
+    ``VFA_FORCE_TORCH_OPS=1`` take the cat / add / ``layer_norm``
+    composition."""
+    if (_use_hip(pe) and pe.shape[-1] % 8 == 0
+            and pe.dtype in (torch.bfloat16, torch.float16, torch.float32)):
+        return _ext.clip_embed_ln(pe.contiguous(), cls, pos, weight, bias,
+                                  eps)
+    c = cls.to(pe.dtype).expand(pe.shape[0], 1, -1)
+    x = torch.cat([c, pe], dim=1) + pos.to(pe.dtype)
+    return layer_norm(x, weight, bias, eps)
+
+
 def preprocess_u8_chw(frames_u8: torch.Tensor, mean, std,
                       bf16: bool = True) -> torch.Tensor:
     """(T, H, W, 3) uint8 → (T, 3, H, W) normalized bf16/f32 in one fused

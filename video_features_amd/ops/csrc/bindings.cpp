@@ -62,6 +62,9 @@ void vfa_attnpool_tokens(const void*, const void*, void*, long long, int, int,
                          hipStream_t);
 void vfa_attention_pool_d64(const void*, const void*, void*, long long, int,
                             int, float, hipStream_t);
+void vfa_clip_embed_ln(const void*, const void*, const void*, const void*,
+                       const void*, void*, long long, int, int, float, int,
+                       hipStream_t);
 }
 
 namespace {
@@ -106,6 +109,31 @@ torch::Tensor layer_norm(torch::Tensor x, torch::Tensor w, torch::Tensor b,
   auto out = torch::empty_like(x);
   vfa_layer_norm(x.data_ptr(), wc.data_ptr(), bc.data_ptr(), out.data_ptr(),
                  x.numel() / d, d, (float)eps, dtype_tag(x), current_stream());
+  return out;
+}
+
+// (T, P, W) patch embeddings + cls (W) + pos (P+1, W) -> ln_pre'd tokens
+// (T, P+1, W); see clip_embed_ln_kernel
+torch::Tensor clip_embed_ln(torch::Tensor pe, torch::Tensor cls,
+                            torch::Tensor pos, torch::Tensor w,
+                            torch::Tensor b, double eps) {
+  TORCH_CHECK(pe.is_cuda() && pe.is_contiguous() && pe.dim() == 3,
+              "clip_embed_ln: pe must be a contiguous (T, P, W) GPU tensor");
+  const long long t = pe.size(0);
+  const int p = (int)pe.size(1), d = (int)pe.size(2);
+  TORCH_CHECK(d % 8 == 0, "clip_embed_ln: W % 8 == 0 required");
+  TORCH_CHECK(cls.numel() == d && w.numel() == d && b.numel() == d &&
+                  pos.dim() == 2 && pos.size(0) == p + 1 && pos.size(1) == d,
+              "clip_embed_ln: shape mismatch");
+  auto cc = cls.contiguous().to(pe.scalar_type());
+  auto pc = pos.contiguous().to(pe.scalar_type());
+  auto wc = w.contiguous().to(pe.scalar_type());
+  auto bc = b.contiguous().to(pe.scalar_type());
+  auto out = torch::empty({(long)t, p + 1, d}, pe.options());
+  vfa_clip_embed_ln(pe.data_ptr(), cc.data_ptr(), pc.data_ptr(),
+                    wc.data_ptr(), bc.data_ptr(), out.data_ptr(),
+                    t * (p + 1), p, d, (float)eps, dtype_tag(pe),
+                    current_stream());
   return out;
 }
 
@@ -612,6 +640,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_qkv", &flash_qkv);
   m.def("mfma_gemm16", &mfma_gemm16);
   m.def("layer_norm_residual", &layer_norm_residual);
+  m.def("clip_embed_ln", &clip_embed_ln);
   m.def("u8_chw_norm", &u8_chw_norm);
   m.def("corr_lookup", &corr_lookup);
   m.def("convex_upsample", &convex_upsample);

@@ -286,6 +286,81 @@ __global__ void layernorm_res_wave_kernel(const T* __restrict__ x,
   }
 }
 
+// CLIP ViT token embedding: [cls | patch embeddings] + positional embedding
+// + ln_pre in one launch, same structure as layernorm_wave_kernel (one wave
+// per output row, 4 rows per block, 16-B accesses, no LDS).
+//   out[t, j] = LN((j == 0 ? cls : pe[t, j - 1]) + pos[j]),  j in [0, p]
+// The sum is formed in f32 in both passes (the second re-reads the sources,
+// which are L2-resident, instead of a rounded intermediate), so the output
+// is rounded once.  Requires d % VEC == 0.
+template <typename T>
+__global__ void clip_embed_ln_kernel(const T* __restrict__ pe,
+                                     const T* __restrict__ cls,
+                                     const T* __restrict__ pos,
+                                     const T* __restrict__ weight,
+                                     const T* __restrict__ bias,
+                                     T* __restrict__ out, long long rows,
+                                     int p, int d, float eps) {
+  constexpr int VEC = 16 / sizeof(T);
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const long long t = row / (p + 1);
+  const int j = (int)(row % (p + 1));
+  const T* x = j == 0 ? cls : pe + (t * p + (j - 1)) * d;
+  const T* pj = pos + (long long)j * d;
+  T* y = out + row * d;
+  using VecT = __attribute__((ext_vector_type(4))) unsigned;
+  const int dvec = d / VEC;
+  float sum = 0.f, sumsq = 0.f;
+  for (int i = lane; i < dvec; i += 64) {
+    T tx[VEC], tp[VEC];
+    *reinterpret_cast<VecT*>(tx) =
+        *reinterpret_cast<const VecT*>(x + (long long)i * VEC);
+    *reinterpret_cast<VecT*>(tp) =
+        *reinterpret_cast<const VecT*>(pj + (long long)i * VEC);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float v = to_f32<T>(tx[e]) + to_f32<T>(tp[e]);
+      sum += v;
+      sumsq += v * v;
+    }
+  }
+  sum = wave_allreduce_sum(sum);
+  sumsq = wave_allreduce_sum(sumsq);
+  const float mean = sum / d;
+  const float rstd = rsqrtf(sumsq / d - mean * mean + eps);
+  for (int i = lane; i < dvec; i += 64) {
+    T tx[VEC], tp[VEC], tw[VEC], tb[VEC];
+    *reinterpret_cast<VecT*>(tx) =
+        *reinterpret_cast<const VecT*>(x + (long long)i * VEC);
+    *reinterpret_cast<VecT*>(tp) =
+        *reinterpret_cast<const VecT*>(pj + (long long)i * VEC);
+    *reinterpret_cast<VecT*>(tw) =
+        *reinterpret_cast<const VecT*>(weight + (long long)i * VEC);
+    *reinterpret_cast<VecT*>(tb) =
+        *reinterpret_cast<const VecT*>(bias + (long long)i * VEC);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float v = (to_f32<T>(tx[e]) + to_f32<T>(tp[e]) - mean) * rstd;
+      tx[e] = from_f32<T>(v * to_f32<T>(tw[e]) + to_f32<T>(tb[e]));
+    }
+    *reinterpret_cast<VecT*>(y + (long long)i * VEC) =
+        *reinterpret_cast<VecT*>(tx);
+  }
+}
+
+template <typename T>
+void launch_clip_embed_ln(const void* pe, const void* cls, const void* pos,
+                          const void* w, const void* b, void* out,
+                          long long rows, int p, int d, float eps,
+                          hipStream_t stream) {
+  const unsigned grid = (unsigned)((rows + 3) / 4);
+  hipLaunchKernelGGL((clip_embed_ln_kernel<T>), dim3(grid), dim3(256), 0,
+                     stream, (const T*)pe, (const T*)cls, (const T*)pos,
+                     (const T*)w, (const T*)b, (T*)out, rows, p, d, eps);
+}
+
 template <typename T>
 void launch_ln(const void* in, const void* w, const void* b, void* out,
                long long rows, int d, float eps, hipStream_t stream) {
@@ -312,6 +387,29 @@ extern "C" void vfa_layer_norm(const void* in, const void* w, const void* b,
     case VFA_BF16:
       launch_ln<__hip_bfloat16>(in, w, b, out, rows, d, eps, stream); break;
     case VFA_F16: launch_ln<__half>(in, w, b, out, rows, d, eps, stream); break;
+  }
+}
+
+// rows = frames * (p + 1); d % 8 == 0 (checked by the binding)
+extern "C" void vfa_clip_embed_ln(const void* pe, const void* cls,
+                                  const void* pos, const void* w,
+                                  const void* b, void* out, long long rows,
+                                  int p, int d, float eps, int dtype,
+                                  hipStream_t stream) {
+  if (rows <= 0) return;
+  switch (dtype) {
+    case VFA_F32:
+      launch_clip_embed_ln<float>(pe, cls, pos, w, b, out, rows, p, d, eps,
+                                  stream);
+      break;
+    case VFA_BF16:
+      launch_clip_embed_ln<__hip_bfloat16>(pe, cls, pos, w, b, out, rows, p,
+                                           d, eps, stream);
+      break;
+    case VFA_F16:
+      launch_clip_embed_ln<__half>(pe, cls, pos, w, b, out, rows, p, d, eps,
+                                   stream);
+      break;
   }
 }
 
