@@ -54,6 +54,7 @@ void vfa_temporal_merge(const void*, void*, int, int, int, int, int, int,
 void vfa_conv2d_nhwc(const void*, const void*, const void*, const void*,
                      const void*, void*, int, int, int, int, int, int, int,
                      int, int, int, int, int, int, int, int, hipStream_t);
+void vfa_conv2d_pick_tile(int, int, int*, int*);
 void vfa_pad2d_nhwc(const void*, void*, int, int, int, int, int, int, int,
                     int, int, hipStream_t);
 void vfa_avgpool2d_nhwc(const void*, void*, long long, int, int, int, int,
@@ -557,6 +558,15 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// (BM, BN) of the tile conv2d_nhwc runs for M = B*OH*OW and kout — the
+// same host function launch_conv calls, so tests can pin a case to a tile
+std::tuple<int64_t, int64_t> conv2d_tile(int64_t m, int64_t kout) {
+  TORCH_CHECK(m > 0 && kout > 0 && m <= INT_MAX && kout <= INT_MAX);
+  int bm = 0, bn = 0;
+  vfa_conv2d_pick_tile((int)m, (int)kout, &bm, &bn);
+  return {bm, bn};
+}
+
 torch::Tensor temporal_merge(torch::Tensor y, int64_t b, int64_t kt,
                              int64_t st, int64_t p0, int64_t p1,
                              bool relu) {
@@ -651,6 +661,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool2d_same", &maxpool2d_same);
   m.def("linear_act", &linear_act);
   m.def("conv2d_nhwc", &conv2d_nhwc);
+  m.def("conv2d_tile", &conv2d_tile);
   m.def("temporal_merge", &temporal_merge);
   m.def("avgpool2d_nhwc", &avgpool2d_nhwc);
   m.def("attnpool_tokens", &attnpool_tokens);

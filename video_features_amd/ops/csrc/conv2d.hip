@@ -30,6 +30,10 @@
 typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
 typedef float f32x4c __attribute__((ext_vector_type(4)));
 
+// the one copy of the tile choice (defined below; also bound to Python as
+// _ext.conv2d_tile so a test can assert which kernel a shape runs)
+extern "C" void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn);
+
 namespace {
 
 constexpr int BK = 64;
@@ -334,21 +338,11 @@ void launch_conv(const void* x, const void* w, const void* bias,
                  const void* res, const void* zp, void* out,
                  const ConvGeom& g, int ldc, hipStream_t stream) {
   const int m = g.b * g.oh * g.ow;
-  // pick the tile minimizing padded work, preferring the bigger tile when
-  // waste ties and the grid still fills the chip (256 CUs)
-  auto cost = [&](int bm, int bn, long long min_wgs) {
-    const long long tm = (m + bm - 1) / bm, tn = (g.kout + bn - 1) / bn;
-    long long padded = tm * bm * tn * bn;
-    if (tm * tn < min_wgs) padded = padded * 4;   // fill penalty
-    return padded;
-  };
-  const long long c256 = (g.kout >= 256 && m >= 4096)
-                             ? cost(256, 256, 150) : (1LL << 62);
-  const long long c128 = cost(128, 128, 120);
-  const long long c64 = cost(256, 64, 120);
-  if (c256 <= c128 && c256 <= c64)
+  int bm, bn;
+  vfa_conv2d_pick_tile(m, g.kout, &bm, &bn);
+  if (bm == 256 && bn == 256)
     launch_cfg<ACT, 256, 256, 8, 4>(x, w, bias, res, zp, out, g, m, ldc, stream);
-  else if (c64 < c128)
+  else if (bm == 256)
     launch_cfg<ACT, 256, 64, 4, 1>(x, w, bias, res, zp, out, g, m, ldc, stream);
   else
     launch_cfg<ACT, 128, 128, 4, 2>(x, w, bias, res, zp, out, g, m, ldc, stream);
@@ -395,6 +389,29 @@ __global__ void pad2d_nhwc_kernel(const __bf16* __restrict__ x,
 }  // namespace
 
 extern "C" {
+
+// Tile (BM x BN) launch_conv runs for M = B*OH*OW output pixels and kout
+// channels: the one minimizing padded work, preferring the bigger tile
+// when waste ties and the grid still fills the chip (256 CUs).
+void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn) {
+  auto cost = [&](int tbm, int tbn, long long min_wgs) {
+    const long long tm = (m + tbm - 1) / tbm, tn = (kout + tbn - 1) / tbn;
+    long long padded = tm * tbm * tn * tbn;
+    if (tm * tn < min_wgs) padded = padded * 4;   // fill penalty
+    return padded;
+  };
+  const long long c256 = (kout >= 256 && m >= 4096)
+                             ? cost(256, 256, 150) : (1LL << 62);
+  const long long c128 = cost(128, 128, 120);
+  const long long c64 = cost(256, 64, 120);
+  if (c256 <= c128 && c256 <= c64) {
+    *bm = 256; *bn = 256;
+  } else if (c64 < c128) {
+    *bm = 256; *bn = 64;
+  } else {
+    *bm = 128; *bn = 128;
+  }
+}
 
 // act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
 // pt/pl: inline zero-pad applied by the kernel (zp = 1 KiB zero page);
