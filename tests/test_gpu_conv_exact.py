@@ -86,7 +86,8 @@ TINY_N_CASES = {
 # as printed by measure_act_floor() below on the CPU:
 #   leaky_relu 5.722e-07, quick_gelu 4.058e-07, gelu 2.477e-07
 # The comparison allows 4x these, because the kernel evaluates the
-# activation with __expf / tanhf and not with torch's routines.
+# activation with v_exp_f32 / v_rcp_f32 / tanhf (act_f in mfma_tile.h) and
+# not with torch's routines.
 ACT_FLOOR = {'leaky_relu': 5.722e-07, 'quick_gelu': 4.058e-07,
              'gelu': 2.477e-07}
 FLOOR_MARGIN = 4.0
@@ -117,7 +118,7 @@ def _geom(shape):
 
 
 def _act64(y, act):
-    """The activation in float64 (the kernel's formulas, conv_act_f)."""
+    """The activation in float64 (the kernel's formulas, act_f)."""
     if act == 'relu':
         return y.relu()
     if act == 'leaky_relu':

@@ -324,16 +324,20 @@ def instance_norm(x: torch.Tensor, eps: float = 1e-5, relu: bool = False,
     return torch.nn.functional.relu(y) if relu else y
 
 
+def _pad1(n, k, s):
+    """TF-SAME (before, after) zero padding of one dim: size n, window k,
+    stride s; the odd cell goes at the end."""
+    total = max(k - s, 0) if n % s == 0 else max(k - (n % s), 0)
+    return total // 2, total - total // 2
+
+
 def maxpool3d_same(x: torch.Tensor, kernel, stride) -> torch.Tensor:
     """TF-SAME max_pool3d (zero padding, asymmetric, extra cell at the end —
     reference i3d_net.py:108-120).  GPU: one fused kernel, no padded copy,
     no argmax indices."""
-    def _pad1(n, k, s):
-        total = max(k - s, 0) if n % s == 0 else max(k - (n % s), 0)
-        return total // 2, total - total // 2
-
     t, h, w = x.shape[-3:]
-    pt, ph, pw = _pad1(t, kernel[0], stride[0]), _pad1(h, kernel[1], stride[1]),         _pad1(w, kernel[2], stride[2])
+    pt, ph, pw = (_pad1(t, kernel[0], stride[0]), _pad1(h, kernel[1], stride[1]),
+                  _pad1(w, kernel[2], stride[2]))
     if _use_hip(x):
         out_sz = [(t + pt[0] + pt[1] - kernel[0]) // stride[0] + 1,
                   (h + ph[0] + ph[1] - kernel[1]) // stride[1] + 1,
@@ -350,10 +354,6 @@ def maxpool2d_same(x: torch.Tensor, kernel, stride,
     """Spatial TF-SAME max_pool2d (zero padding, extra cell at the end) —
     the spatial half of I3D's TF-SAME 3D pools in the flattened
     (B*T, C, H, W) path; the temporal half is a shifted elementwise max."""
-    def _pad1(n, k, s):
-        total = max(k - s, 0) if n % s == 0 else max(k - (n % s), 0)
-        return total // 2, total - total // 2
-
     h, w = x.shape[-2:]
     ph, pw = _pad1(h, kernel[0], stride[0]), _pad1(w, kernel[1], stride[1])
     if _use_hip(x):
@@ -466,6 +466,27 @@ _ACT_IDS = {'none': 0, 'relu': 1, 'quick_gelu': 2, 'gelu': 3,
             'leaky_relu': 4}
 
 
+def _act_id(act: str) -> int:
+    if act not in _ACT_IDS:
+        raise ValueError(f'unknown activation {act!r}; expected one of '
+                         f'{sorted(_ACT_IDS)}')
+    return _ACT_IDS[act]
+
+
+def _apply_act(y: torch.Tensor, act: str) -> torch.Tensor:
+    """The torch form of the kernels' fused epilogue activation."""
+    _act_id(act)
+    if act == 'relu':
+        return torch.nn.functional.relu(y)
+    if act == 'quick_gelu':
+        return y * torch.sigmoid(1.702 * y)
+    if act == 'gelu':
+        return torch.nn.functional.gelu(y, approximate='tanh')
+    if act == 'leaky_relu':
+        return torch.nn.functional.leaky_relu(y, 0.1)
+    return y
+
+
 def linear_act(x: torch.Tensor, weight: torch.Tensor,
                bias: Optional[torch.Tensor] = None,
                act: str = 'none',
@@ -482,20 +503,12 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor,
         x2 = x.reshape(-1, k).contiguous()
         r2 = res.reshape(-1, n).contiguous() if res is not None else None
         out = _ext.linear_act(x2, weight.contiguous(), bias, r2,
-                              _ACT_IDS[act])
+                              _act_id(act))
         return out.reshape(*x.shape[:-1], n)
     y = torch.nn.functional.linear(x, weight, bias)
     if res is not None:
         y = y + res.reshape(y.shape)
-    if act == 'relu':
-        return torch.nn.functional.relu(y)
-    if act == 'quick_gelu':
-        return y * torch.sigmoid(1.702 * y)
-    if act == 'gelu':
-        return torch.nn.functional.gelu(y, approximate='tanh')
-    if act == 'leaky_relu':
-        return torch.nn.functional.leaky_relu(y, 0.1)
-    return y
+    return _apply_act(y, act)
 
 
 def temporal_merge_fused(y: torch.Tensor, b: int, kt: int, st: int,
@@ -569,7 +582,7 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
         r = res.contiguous(memory_format=torch.channels_last) \
             if res is not None else None
         return _ext.conv2d_nhwc(x, w_cl, bias, r, sh, sw, pt, pb, pl, pr,
-                                _ACT_IDS[act], out, out_off)
+                                _act_id(act), out, out_off)
     if weight.shape[1] > x.shape[1]:
         # caller passed a channel-padded weight but the GPU path declined
         # (VFA_NO_CONV, forced torch ops, ...): slice the zero pad back off
@@ -582,14 +595,7 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
         y = torch.nn.functional.conv2d(x, weight, bias, (sh, sw), (pt, pl))
     if res is not None:
         y = y + res
-    if act == 'relu':
-        y = torch.nn.functional.relu(y)
-    elif act == 'quick_gelu':
-        y = y * torch.sigmoid(1.702 * y)
-    elif act == 'gelu':
-        y = torch.nn.functional.gelu(y, approximate='tanh')
-    elif act == 'leaky_relu':
-        y = torch.nn.functional.leaky_relu(y, 0.1)
+    y = _apply_act(y, act)
     if out is not None:
         out[:, out_off:out_off + y.shape[1]] = y
         return out
@@ -651,15 +657,7 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
     y = conv(x)
     if res is not None:
         y = y + res
-    if act == 'relu':
-        y = torch.nn.functional.relu(y)
-    elif act == 'leaky_relu':
-        y = torch.nn.functional.leaky_relu(y, 0.1)
-    elif act == 'quick_gelu':
-        y = y * torch.sigmoid(1.702 * y)
-    elif act == 'gelu':
-        y = torch.nn.functional.gelu(y, approximate='tanh')
-    return y
+    return _apply_act(y, act)
 
 
 def grid_sample_bilinear(x: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:

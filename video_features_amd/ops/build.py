@@ -23,8 +23,12 @@ def _torch_paths():
 
 
 def _newer(src: Path, obj: Path) -> bool:
-    return (not obj.exists() or obj.stat().st_mtime < src.stat().st_mtime
-            or obj.stat().st_mtime < (CSRC / 'vfa_common.h').stat().st_mtime)
+    """True when ``obj`` is missing or older than ``src`` or than any header
+    beside ``src`` (every ``*.h`` is a dependency of every object)."""
+    if not obj.exists():
+        return True
+    deps = [src, *src.parent.glob('*.h')]
+    return any(obj.stat().st_mtime < d.stat().st_mtime for d in deps)
 
 
 def build(verbose: bool = True) -> Path:

@@ -17,43 +17,21 @@
 // so weights need NO reshuffling and B staging is identical to the linear
 // kernel's.
 //
-// Machinery shared with gemm.hip (cdna_hip_programming.md §5): 256x256 /
-// 128x128 tiles, BK=64, double-buffered LDS staged by
-// __builtin_amdgcn_global_load_lds width 16 with the conflict-free XOR
-// swizzle (cswz) on the per-lane *source* address (lane-linear LDS
-// image), glds for
-// the next K-tile spread across the current tile's two MFMA half-steps,
-// mfma_f32_16x16x32_bf16, fused bias+activation(+residual) epilogue.
-// Requires C % 8 == 0 (each lane's 16-B segment stays inside one tap).
-#include "vfa_common.h"
-
-typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
-typedef float f32x4c __attribute__((ext_vector_type(4)));
+// The tile machinery is mfma_tile.h, shared with gemm.hip: 256x256 /
+// 128x128 / 256x64 tiles, BK=64, double-buffered LDS staged by glds with
+// the conflict-free XOR swizzle on the per-lane *source* address, the
+// K-step (the next K-tile's glds spread across its two MFMA half-steps),
+// the fused bias+activation(+residual) epilogue.  This file adds the A
+// operand's im2col staging, the guarded W staging, the K loop around the
+// shared K-step, the pad pass and the tile choice.  Requires C % 8 == 0
+// (each lane's 16-B segment stays inside one tap).
+#include "mfma_tile.h"
 
 // the one copy of the tile choice (defined below; also bound to Python as
 // _ext.conv2d_tile so a test can assert which kernel a shape runs)
 extern "C" void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn);
 
 namespace {
-
-constexpr int BK = 64;
-
-// see gemm.hip swz(): conflict-free row-slot XOR ((row>>1)&7, searched
-// against gfx950's REAL mixed b128 lane groups) for the 128-B-row images
-__device__ __forceinline__ int cswz(int byte_off) {
-  return byte_off ^ (((byte_off >> 8) & 7) << 4);
-}
-
-__device__ __forceinline__ float conv_act_f(float x, int kind) {
-  if (kind == 1) return fmaxf(x, 0.f);
-  if (kind == 2) return x / (1.0f + __expf(-1.702f * x));  // QuickGELU
-  if (kind == 3) {
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    return 0.5f * x * (1.0f + tanhf(k0 * (x + k1 * x * x * x)));
-  }
-  if (kind == 4) return fmaxf(x, 0.f) + 0.1f * fminf(x, 0.f);  // LeakyReLU .1
-  return x;
-}
 
 struct ConvGeom {
   int b, hp, wp, cin;       // input dims as addressed (REAL h/w when the
@@ -117,30 +95,6 @@ __device__ __forceinline__ void conv_stage_a(
   }
 }
 
-// Weight staging == linear kernel's stage_glds (W is (N, Kr) row-major).
-template <int ROWS, int WAVES>
-__device__ __forceinline__ void conv_stage_w(
-    const __bf16* __restrict__ wgt, long long row_stride, char* lds_base,
-    int wave, int lane, int piece, int npieces) {
-  constexpr int NSUB = ROWS * 128 / 1024;
-  constexpr int PER_WAVE = NSUB / WAVES;
-  // subtile-local swizzle; f = ((sub&1)<<2)|(r_in>>1) (see gemm.hip)
-  const int off = lane * 16;
-  const int r_in = off >> 7;
-#pragma unroll
-  for (int i = 0; i < PER_WAVE; ++i) {
-    if (piece >= 0 && (i * npieces) / PER_WAVE != piece) continue;
-    const int sub = wave * PER_WAVE + i;
-    const int b_in = (off & 127) ^
-                     ((((sub & 1) << 2) | (r_in >> 1)) << 4);
-    const __bf16* src = wgt + (long long)(sub * 8 + r_in) * row_stride;
-    __builtin_amdgcn_global_load_lds(
-        reinterpret_cast<const unsigned int*>(
-            reinterpret_cast<const char*>(src) + b_in),
-        reinterpret_cast<unsigned int*>(lds_base + sub * 1024), 16, 0, 0);
-  }
-}
-
 // Bounds-checked A staging (M-edge tiles and the ragged last K-tile):
 // same LDS image, zero fill (covers out-of-image taps too).
 template <int ROWS, int THREADS>
@@ -163,10 +117,14 @@ __device__ __forceinline__ void conv_guard_a(
         v = *reinterpret_cast<const uint4*>(
             x + pr.base + ((long long)iy * g.wp + ix) * g.cin + c);
     }
-    *reinterpret_cast<uint4*>(lds_base + cswz(row * 128 + seg * 16)) = v;
+    *reinterpret_cast<uint4*>(lds_base + swz(row * 128 + seg * 16)) = v;
   }
 }
 
+// Bounds-checked W staging.  What mfma_tile.h's stage_guard does when
+// Kr % 8 == 0, kept as its own 16-B-only loop: with stage_guard here the
+// 256x256 tile (256 VGPRs, spilling) measured 3-6% slower on its full-tile
+// rows (profiles/mfma_tile_refactor.md).
 template <int ROWS, int THREADS>
 __device__ __forceinline__ void conv_guard_w(
     const __bf16* __restrict__ wgt, long long row_stride, int n0, int ntotal,
@@ -178,7 +136,7 @@ __device__ __forceinline__ void conv_guard_w(
       v = *reinterpret_cast<const uint4*>(wgt + (long long)row * row_stride +
                                           seg * 8);
     }
-    *reinterpret_cast<uint4*>(lds_base + cswz(row * 128 + seg * 16)) = v;
+    *reinterpret_cast<uint4*>(lds_base + swz(row * 128 + seg * 16)) = v;
   }
 }
 
@@ -196,7 +154,6 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
                         int ldc, int tiles_m, int tiles_n) {
   constexpr int MI = BM / (WAVES / WN) / 16;   // 16-row MFMA tiles / wave
   constexpr int NJ = BN / WN / 16;             // 16-col MFMA tiles / wave
-  static_assert(NJ == 4, "epilogue assumes 4 column fragments per wave");
   constexpr int TILE_A = BM * BK * 2, TILE_B = BN * BK * 2;
   constexpr int THREADS = WAVES * 64;
   constexpr int PER_WAVE = (BM * 128 / 1024) / WAVES;
@@ -205,18 +162,11 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
   auto sA = [&](int buf) { return smem + buf * (TILE_A + TILE_B); };
   auto sB = [&](int buf) { return smem + buf * (TILE_A + TILE_B) + TILE_A; };
 
-  const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int xcd = wg % 8, orig = wg / 8;
-    const int q = nwg / 8, r = nwg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig;
-  }
+  const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   const int tile_n = wg / tiles_m, tile_m = wg % tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = lane & 15, hi4 = lane >> 4;
   const int wm = wave / WN, wn = wave % WN;
 
   const int kr = g.kr, n = g.kout;
@@ -242,8 +192,8 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
     if (tile_full && (kfull || kt + 1 < nk)) {
       conv_stage_a<BM, WAVES>(x, zp, g, aref, k0, sA(buf), wave, lane,
                               kfrac0, a_rin >> 1, -1, 1);
-      conv_stage_w<BN, WAVES>(wgt + (long long)n0 * kr + k0, kr, sB(buf),
-                              wave, lane, -1, 1);
+      stage_glds<BN, WAVES>(wgt + (long long)n0 * kr + k0, kr, sB(buf),
+                            wave, lane);
     } else {
       conv_guard_a<BM, THREADS>(x, g, m0, mtotal, k0, sA(buf), threadIdx.x);
       conv_guard_w<BN, THREADS>(wgt + (long long)n0 * kr + k0, kr, n0, n,
@@ -253,11 +203,11 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
 
   stage(0, 0);
 
-  f32x4c acc[MI][NJ];
+  f32x4 acc[MI][NJ];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4c{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
@@ -268,55 +218,23 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
     if ((kt + 1 < nk) && !glds_nxt) stage(1 - cur, kt + 1);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      bf16x8c afr[MI], bfr[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int brow = wn * (NJ * 16) + j * 16 + lo;
-        bfr[j] = *reinterpret_cast<const bf16x8c*>(
-            sB(cur) + cswz(brow * 128 + kk * 64 + hi4 * 16));
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int arow = wm * (MI * 16) + i * 16 + lo;
-        afr[i] = *reinterpret_cast<const bf16x8c*>(
-            sA(cur) + cswz(arow * 128 + kk * 64 + hi4 * 16));
-      }
-      if (glds_nxt) {
-        conv_stage_a<BM, WAVES>(x, zp, g, aref, k0_nxt, sA(1 - cur), wave,
-                                lane, kfrac0, a_rin >> 1, kk, 2);
-        conv_stage_w<BN, WAVES>(wgt + (long long)n0 * kr + k0_nxt, kr,
-                                sB(1 - cur), wave, lane, kk, 2);
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afr[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
+      mfma_kstep<MI, NJ>(sA(cur), sB(cur), wm * (MI * 16), wn * (NJ * 16),
+                         kk, lane, acc, [&] {
+        if (glds_nxt) {
+          conv_stage_a<BM, WAVES>(x, zp, g, aref, k0_nxt, sA(1 - cur), wave,
+                                  lane, kfrac0, a_rin >> 1, kk, 2);
+          stage_glds_piece<BN, WAVES>(wgt + (long long)n0 * kr + k0_nxt, kr,
+                                      sB(1 - cur), wave, lane, kk, 2);
+        }
+      });
     }
   }
 
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int col = n0 + wn * (NJ * 16) + j * 16 + lo;
-    if (!tile_full && col >= n) continue;
-    const float bv = bias ? (float)bias[col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * (MI * 16) + i * 16 + hi4 * 4 + r;
-        if (!tile_full && row >= mtotal) continue;
-        float v = acc[i][j][r] + bv;
-        if (res) v += (float)res[(long long)row * n + col];
-        // ldc > n: writing a channel slice of a wider NHWC buffer (the
-        // caller eliminated a cat copy); res stays logically (M, n)
-        out[(long long)row * ldc + col] = (__bf16)conv_act_f(v, ACT);
-      }
-    }
-  }
+  // ldc > n: writing a channel slice of a wider NHWC buffer (the caller
+  // eliminated a cat copy); res stays logically (M, n)
+  epilogue_frag<ACT, MI, NJ, 2>(acc, bias, res, out, mtotal, n, ldc,
+                                m0 + wm * (MI * 16), n0 + wn * (NJ * 16),
+                                lane, !tile_full);
 }
 
 template <int ACT, int BM, int BN, int WAVES, int WN>
@@ -425,13 +343,10 @@ void vfa_conv2d_nhwc(const void* x, const void* w, const void* bias,
                      int ldc, int act, hipStream_t stream) {
   ConvGeom g{b, hp, wp, cin, oh, ow, kout, kh, kw, sh, sw, pt, pl,
              kh * kw * cin};
-  switch (act) {
-    case 0: launch_conv<0>(x, w, bias, res, zp, out, g, ldc, stream); break;
-    case 1: launch_conv<1>(x, w, bias, res, zp, out, g, ldc, stream); break;
-    case 2: launch_conv<2>(x, w, bias, res, zp, out, g, ldc, stream); break;
-    case 3: launch_conv<3>(x, w, bias, res, zp, out, g, ldc, stream); break;
-    case 4: launch_conv<4>(x, w, bias, res, zp, out, g, ldc, stream); break;
-  }
+  dispatch_act(act, [&](auto id) {
+    launch_conv<decltype(id)::value>(x, w, bias, res, zp, out, g, ldc,
+                                     stream);
+  });
 }
 
 void vfa_pad2d_nhwc(const void* x, void* out, int b, int h, int w, int cin,

@@ -18,58 +18,15 @@
 //
 // Structure (cdna_hip_programming.md §5): BIG tiles 256x256 (8 waves as
 // 2M x 4N, 128x64 C per wave, 128 KiB LDS) for the transformer shapes,
-// 128x128 (4 waves, 2x2) when N < 256 or M is small.  BK = 64.  Both
-// operands stage through LDS as [row][64] bf16 images (A rows = m, B rows
-// = n; the B fragment of C[m][n] = dot_k A[m][k] W[n][k] reads the same
-// row-major image as A).  Staging uses __builtin_amdgcn_global_load_lds
-// width 16 (2 LDS buffers, next K-tile in flight during compute), with a
-// conflict-free XOR swizzle (see swz() below) applied to the *global
-// source* address so the LDS image stays lane-linear for glds;
-// ds_read_b128 fragment reads apply the same XOR.
-// Partial tiles (M/N/K tails) take a bounds-checked vector-staging path
-// with an identical LDS image.
-#include "vfa_common.h"
+// 128x128 (4 waves, 2x2) when N < 256 or M is small.  The tile machinery —
+// LDS swizzle, glds / guarded staging, the K-step, the fragment-layout
+// epilogue, the activation table — is mfma_tile.h, shared with
+// conv2d.hip; this file holds the kernels' K loops and tile walks, the
+// vectorised 256^2 epilogue and the routing.
+#include "mfma_tile.h"
 #include <cstdlib>
-#include <type_traits>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-constexpr int BK = 64;
-
-// LDS bank swizzle for the [row][64]-bf16 (128-B row) images, read as
-// ds_read_b128.  gfx950's b128 lane groups MIX lo and hi4 lanes
-// (MI355X_MICROARCH §LDS: {0-3,12-15,20-27}...), so the fix was searched
-// against the REAL group tables: XOR byte bits 4..6 with (row>>1)&7 is
-// conflict-free for every (group, kk, row-parity) combination of this
-// read pattern, where the st_16x32 one-bit variant left 2-way
-// (PMC: 6.4e8 conflict cycles per probe run).  Involution (the XOR value
-// depends only on row bits, which it does not touch), 16-B granular,
-// within-row — glds-compatible on the source side.
-__device__ __forceinline__ int swz(int byte_off) {
-  return byte_off ^ (((byte_off >> 8) & 7) << 4);
-}
-
-// act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
-__device__ __forceinline__ float act_f(float x, int kind) {
-  if (kind == 1) return fmaxf(x, 0.f);
-  if (kind == 2) {
-    // QuickGELU x*sigmoid(1.702x) as x * rcp(1 + exp2(c*x)), c folded:
-    // one v_exp_f32 + one v_rcp_f32 + 3 VALU, where the IEEE division of
-    // x / (1 + __expf(..)) cost ~25 instructions per element.  Both
-    // approximations are ~1 ulp in f32, far below the bf16 output step.
-    const float c = -1.702f * 1.4426950408889634f;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(c * x));
-  }
-  if (kind == 3) {
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    return 0.5f * x * (1.0f + tanhf(k0 * (x + k1 * x * x * x)));
-  }
-  if (kind == 4) return x > 0.f ? x : 0.1f * x;
-  return x;
-}
 
 // Shared full-tile epilogue of the two 256x256 kernels: one wave's 128x64
 // f32 accumulator block (8x4 MFMA tiles) -> bias + residual + activation
@@ -131,79 +88,6 @@ __device__ __forceinline__ void epilogue_strips(
   }
 }
 
-// XCD-aware bijective remap (consecutive remapped ids share an XCD)
-__device__ __forceinline__ int xcd_remap(int wg, int nwg) {
-  const int xcd = wg % 8, orig = wg / 8;
-  const int q = nwg / 8, r = nwg % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig;
-}
-
-// stage a (ROWS x 64) bf16 tile into a swizzled LDS image (see swz())
-// via glds; each wave covers (ROWS*128/1024)/WAVES subtiles.
-// PIECES > 1 splits the wave's subtiles into issue groups so the glds for
-// the next K-tile can be spread across the current tile's MFMA quadrants
-// (piece = which group to issue; -1 = all).
-template <int ROWS, int WAVES>
-__device__ __forceinline__ void stage_glds_piece(
-    const __bf16* __restrict__ g, long long row_stride_elems, char* lds_base,
-    int wave, int lane, int piece, int npieces) {
-  constexpr int NSUB = ROWS * 128 / 1024;
-  constexpr int PER_WAVE = NSUB / WAVES;
-  // full-tile row = sub*8 + r_in, so the swizzle value f = (row>>1)&7
-  // = ((sub&1)<<2) | (r_in>>1) varies with the SUBTILE parity
-  const int off = lane * 16;                   // linear LDS offset in subtile
-  const int r_in = off >> 7;                   // row within subtile
-#pragma unroll
-  for (int i = 0; i < PER_WAVE; ++i) {
-    if (piece >= 0 && (i * npieces) / PER_WAVE != piece) continue;
-    const int sub = wave * PER_WAVE + i;
-    const int b_in = (off & 127) ^
-                     ((((sub & 1) << 2) | (r_in >> 1)) << 4);
-    const __bf16* src = g + (long long)(sub * 8 + r_in) * row_stride_elems;
-    // LDS destination is wave-uniform base + lane*16 (hardware-added);
-    // the per-lane *global* address carries the swizzle
-    __builtin_amdgcn_global_load_lds(
-        reinterpret_cast<const unsigned int*>(
-            reinterpret_cast<const char*>(src) + b_in),
-        reinterpret_cast<unsigned int*>(lds_base + sub * 1024), 16, 0, 0);
-  }
-}
-
-template <int ROWS, int WAVES>
-__device__ __forceinline__ void stage_glds(const __bf16* __restrict__ g,
-                                           long long row_stride_elems,
-                                           char* lds_base, int wave,
-                                           int lane) {
-  stage_glds_piece<ROWS, WAVES>(g, row_stride_elems, lds_base, wave, lane,
-                                -1, 1);
-}
-
-// bounds-checked fallback staging (tails): same LDS image, zero fill.
-template <int ROWS, int THREADS>
-__device__ __forceinline__ void stage_guard(const __bf16* __restrict__ g,
-                                            long long row_stride_elems,
-                                            int valid_rows, int valid_k,
-                                            char* lds_base, int tid) {
-  for (int t = tid; t < ROWS * 8; t += THREADS) {   // 8 16-B segs per row
-    const int row = t >> 3, seg = t & 7;
-    bf16x8 v{};
-    if (row < valid_rows && seg * 8 < valid_k) {
-      if ((seg + 1) * 8 <= valid_k) {
-        v = *reinterpret_cast<const bf16x8*>(g + row * row_stride_elems +
-                                             seg * 8);
-      } else {
-        // compile-time element index: a runtime-indexed local goes to
-        // scratch
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (seg * 8 + j < valid_k)
-            v[j] = g[row * row_stride_elems + seg * 8 + j];
-      }
-    }
-    *reinterpret_cast<bf16x8*>(lds_base + swz(row * 128 + seg * 16)) = v;
-  }
-}
-
 // BIG: 256x256 tile, 8 waves (2Mx4N), 128x64 C per wave (8x4 MFMA tiles).
 // else: 128x128 tile, 4 waves (2x2), 64x64 per wave (4x4 tiles).
 template <int ACT, bool FULL, bool BIG>
@@ -236,7 +120,6 @@ void linear_act_kernel(const __bf16* __restrict__ a,
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = lane & 15, hi4 = lane >> 4;
   const int wm = wave / WN, wn = wave % WN;
 
   const int nk = (k + BK - 1) / BK;
@@ -281,75 +164,28 @@ void linear_act_kernel(const __bf16* __restrict__ a,
     // bursting at the barrier (PMC: 39% of wave cycles were parked)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {           // two 32-deep MFMA steps
-      bf16x8 afr[MI], bfr[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int brow = wn * (NJ * 16) + j * 16 + lo;
-        bfr[j] = *reinterpret_cast<const bf16x8*>(
-            sB(cur) + swz(brow * 128 + kk * 64 + hi4 * 16));
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int arow = wm * (MI * 16) + i * 16 + lo;
-        afr[i] = *reinterpret_cast<const bf16x8*>(
-            sA(cur) + swz(arow * 128 + kk * 64 + hi4 * 16));
-      }
-      if (glds_nxt) {
-        stage_glds_piece<BM, WAVES>(a + (long long)m0 * k + ko_nxt, k,
-                                    sA(1 - cur), wave, lane, kk, 2);
-        stage_glds_piece<BN, WAVES>(w + (long long)n0 * k + ko_nxt, k,
-                                    sB(1 - cur), wave, lane, kk, 2);
-      }
-      __builtin_amdgcn_s_setprio(1);   // keep the MFMA cluster issuing
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afr[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
+      mfma_kstep<MI, NJ>(sA(cur), sB(cur), wm * (MI * 16), wn * (NJ * 16),
+                         kk, lane, acc, [&] {
+        if (glds_nxt) {
+          stage_glds_piece<BM, WAVES>(a + (long long)m0 * k + ko_nxt, k,
+                                      sA(1 - cur), wave, lane, kk, 2);
+          stage_glds_piece<BN, WAVES>(w + (long long)n0 * k + ko_nxt, k,
+                                      sB(1 - cur), wave, lane, kk, 2);
+        }
+      });
     }
     // no trailing barrier: the next iteration's top __syncthreads() both
     // drains the in-flight glds and orders reads before buffer reuse
   }
 
-  // epilogue: bias + residual + activation, bf16 store in the fragment
-  // layout.  The bounds guards and the residual test are hoisted: four
-  // specialisations picked by two block-uniform branches, so interior
-  // tiles run no per-element compare and edge tiles no per-element
-  // null test.  (The 256^2 hot path is linear256p_kernel's epilogue; this
-  // one serves the small tile and the edge / ragged-K tiles.)
-  auto epilogue = [&](auto guarded, auto has_res) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int col = n0 + wn * (NJ * 16) + j * 16 + lo;
-      if (guarded.value && col >= n) continue;
-      const float bv = bias ? (float)bias[col] : 0.f;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = m0 + wm * (MI * 16) + i * 16 + hi4 * 4 + r;
-          if (guarded.value && row >= m) continue;
-          float v = acc[i][j][r] + bv;
-          if (has_res.value && (!BIG || res))
-            v += (float)res[(long long)row * n + col];
-          c[(long long)row * n + col] = (__bf16)act_f(v, ACT);
-        }
-      }
-    }
-  };
-  using T = std::true_type;
-  using F = std::false_type;
-  if (BIG) {
-    // edge column / ragged-K tiles only, at 256 VGPRs: splitting on the
-    // residual as well spills 8-12 registers, so that test stays inside
-    if (tile_full) epilogue(F{}, T{}); else epilogue(T{}, T{});
-  } else if (tile_full) {
-    if (res) epilogue(F{}, T{}); else epilogue(F{}, F{});
-  } else {
-    if (res) epilogue(T{}, T{}); else epilogue(T{}, F{});
-  }
+  // fragment-layout epilogue, guards hoisted.  (The 256^2 hot path is
+  // linear256p_kernel's epilogue; this one serves the small tile and the
+  // edge / ragged-K tiles.)  BIG: edge column / ragged-K tiles only, at 256
+  // VGPRs: splitting on the residual as well spills 8-12 registers, so
+  // that test stays inside
+  epilogue_frag_hoisted<ACT, MI, NJ, !BIG>(
+      tile_full, acc, bias, res, c, m, n, n, m0 + wm * (MI * 16),
+      n0 + wn * (NJ * 16), lane);
 }
 
 // ------------------------------------------------- persistent 256^2 tiles
@@ -383,7 +219,6 @@ void linear256p_kernel(const __bf16* __restrict__ a,
   auto sB = [&](int buf) { return smem_p + buf * (2 * TILE) + TILE; };
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = lane & 15, hi4 = lane >> 4;
   const int wm = wave >> 2, wn = wave & 3;
   float* ep = reinterpret_cast<float*>(smem_p + 4 * TILE) + wave * (16 * 64);
 
@@ -427,31 +262,13 @@ void linear256p_kernel(const __bf16* __restrict__ a,
       const bool issue = !last || more;
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {         // two 32-deep MFMA steps
-        bf16x8 afr[8], bfr[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int brow = wn * 64 + j * 16 + lo;
-          bfr[j] = *reinterpret_cast<const bf16x8*>(
-              sB(cur) + swz(brow * 128 + kk * 64 + hi4 * 16));
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int arow = wm * 128 + i * 16 + lo;
-          afr[i] = *reinterpret_cast<const bf16x8*>(
-              sA(cur) + swz(arow * 128 + kk * 64 + hi4 * 16));
-        }
-        if (issue) {
-          stage_glds_piece<256, 8>(an, k, sA(1 - cur), wave, lane, kk, 2);
-          stage_glds_piece<256, 8>(wn_, k, sB(1 - cur), wave, lane, kk, 2);
-        }
-        __builtin_amdgcn_s_setprio(1);   // keep the MFMA cluster issuing
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                afr[i], bfr[j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
+        mfma_kstep<8, 4>(sA(cur), sB(cur), wm * 128, wn * 64, kk, lane, acc,
+                         [&] {
+          if (issue) {
+            stage_glds_piece<256, 8>(an, k, sA(1 - cur), wave, lane, kk, 2);
+            stage_glds_piece<256, 8>(wn_, k, sB(1 - cur), wave, lane, kk, 2);
+          }
+        });
       }
     }
 
@@ -920,14 +737,10 @@ extern "C" {
 void vfa_linear_act(const void* a, const void* w, const void* bias,
                     const void* res, void* c, int m, int n, int k, int act,
                     hipStream_t stream) {
-  switch (act) {
-    case 0: launch_linear<0>(a, w, bias, res, c, m, n, k, stream); break;
-    case 1: launch_linear<1>(a, w, bias, res, c, m, n, k, stream); break;
-    case 2: launch_linear<2>(a, w, bias, res, c, m, n, k, stream); break;
-    case 3: launch_linear<3>(a, w, bias, res, c, m, n, k, stream); break;
-    case 4: launch_linear<4>(a, w, bias, res, c, m, n, k, stream); break;
-    default: break;                            // rejected by the binding
-  }
+  // any other id is rejected by the binding
+  dispatch_act(act, [&](auto id) {
+    launch_linear<decltype(id)::value>(a, w, bias, res, c, m, n, k, stream);
+  });
 }
 
 }  // extern "C"
