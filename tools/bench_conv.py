@@ -5,6 +5,12 @@
 Run on a GPU box:  python tools/bench_conv.py [--iters 50]
 Prints per-shape TF/s for both paths and the ratio; >1.00 means the
 in-tree kernel wins.  Evidence for profiles/ (VERDICT round-1 item 1).
+
+The PWC rows are the decoder / refiner convs at the bench's 256x256 padded
+input, 64 frame pairs.  A dense row is one DenseNet step of a level's
+buffer: in-tree it is ONE slice-in / slice-out call on the channels_last
+buffer, the MIOpen side is what the cat path runs,
+``cat([leaky_relu(conv(x)), x], 1)`` on NCHW.  --only pwc / hot selects.
 """
 import argparse
 import sys
@@ -34,6 +40,16 @@ SHAPES = [
 ]
 
 
+# PWC decoder levels at a 256x256 input: (level, feature channels, H = W)
+PWC_LEVELS = [(2, 32, 64), (3, 64, 32), (4, 96, 16)]
+PWC_DENSE = [128, 128, 96, 64, 32]          # K_out of the five dense convs
+PWC_DENSE_OFF = [320, 192, 96, 32, 0]       # their write offsets
+PWC_B = 64
+# the refiner's dilated convs at level 2: (C, K_out, dilation)
+PWC_REFINER = [(128, 128, 2), (128, 128, 4), (128, 96, 8), (96, 64, 16),
+               (64, 32, 1)]
+
+
 def bench(fn, iters, warmup=10):
     for _ in range(warmup):
         fn()
@@ -51,13 +67,30 @@ def bench(fn, iters, warmup=10):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--iters', type=int, default=50)
+    p.add_argument('--only', choices=['all', 'hot', 'pwc'], default='all')
     args = p.parse_args()
     assert ops.hip_available()
     dev = 'cuda:0'
-    print(f"{'shape':28s} {'TFLOP':>6s} {'vfa ms':>8s} {'vfa TF/s':>9s} "
-          f"{'miopen ms':>9s} {'mi TF/s':>8s} {'ratio':>6s}")
-    wins = 0
-    for name, b, c, h, w, k, kh, kw, st, pad in SHAPES:
+    print(f"{'shape':28s} {'dil':>3s} {'TFLOP':>6s} {'vfa ms':>8s} "
+          f"{'vfa TF/s':>9s} {'miopen ms':>9s} {'mi TF/s':>8s} {'ratio':>6s}")
+    wins = total = 0
+
+    def row(name, dil, flop, t_vfa, t_mi):
+        nonlocal wins, total
+        r = t_mi / t_vfa
+        wins += r >= 1.0
+        total += 1
+        print(f'{name:28s} {dil:3d} {flop / 1e12:6.2f} {t_vfa:8.3f} '
+              f'{flop / t_vfa / 1e9:9.1f} {t_mi:9.3f} '
+              f'{flop / t_mi / 1e9:8.1f} {r:6.2f}')
+
+    def rand_w(k, c, kh, kw):
+        return (torch.randn(k, c, kh, kw, device=dev) *
+                (2.0 / (c * kh * kw)) ** 0.5).to(torch.bfloat16)
+
+    cl = torch.channels_last
+    for name, b, c, h, w, k, kh, kw, st, pad in \
+            (SHAPES if args.only != 'pwc' else []):
         torch.manual_seed(0)
         x = (torch.randn(b, c, h, w, device=dev) * 0.5).to(torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
@@ -73,12 +106,48 @@ def main():
                       args.iters)
         t_mi = bench(
             lambda: F.relu(F.conv2d(x, wg, bias, st, pad)), args.iters)
-        r = t_mi / t_vfa
-        wins += r >= 1.0
-        print(f'{name:28s} {flop / 1e12:6.2f} {t_vfa:8.3f} '
-              f'{flop / t_vfa / 1e9:9.1f} {t_mi:9.3f} '
-              f'{flop / t_mi / 1e9:8.1f} {r:6.2f}')
-    print(f'\n{wins}/{len(SHAPES)} shapes >= MIOpen')
+        row(name, 1, flop, t_vfa, t_mi)
+
+    for lvl, fc, hw in (PWC_LEVELS if args.only != 'hot' else []):
+        cin0 = 81 + fc + 4
+        width = (448 + cin0 + 7) // 8 * 8
+        torch.manual_seed(0)
+        buf = (torch.randn(PWC_B, hw, hw, width, device=dev) * 0.5) \
+            .to(torch.bfloat16).permute(0, 3, 1, 2)
+        c = cin0
+        for i, (k, off) in enumerate(zip(PWC_DENSE, PWC_DENSE_OFF)):
+            c8 = (c + 7) // 8 * 8
+            wg = rand_w(k, c, 3, 3)
+            wg8 = F.pad(wg, (0, 0, 0, 0, 0, c8 - c)).contiguous(
+                memory_format=cl)
+            bias = torch.randn(k, device=dev).to(torch.bfloat16)
+            xn = buf[:, off + k:off + k + c].contiguous()        # NCHW
+            flop = 2.0 * PWC_B * hw * hw * k * 9 * c
+            t_vfa = bench(lambda: ops.conv2d_act(
+                buf, wg8, bias, 1, 1, 'leaky_relu', out=buf, out_off=off,
+                in_off=off + k, in_ch=c8), args.iters)
+            t_mi = bench(lambda: torch.cat(
+                [F.leaky_relu(F.conv2d(xn, wg, bias, 1, 1), 0.1), xn], 1),
+                args.iters)
+            row(f'pwc l{lvl} dense{i + 1} {c}>{k} {hw}²', 1, flop, t_vfa,
+                t_mi)
+            c += k
+
+    for c, k, dil in (PWC_REFINER if args.only != 'hot' else []):
+        torch.manual_seed(0)
+        x = (torch.randn(PWC_B, c, 64, 64, device=dev) * 0.5) \
+            .to(torch.bfloat16).contiguous(memory_format=cl)
+        xn = x.contiguous()                  # the cat path's refiner is NCHW
+        wg = rand_w(k, c, 3, 3)
+        wcl = wg.contiguous(memory_format=cl)
+        bias = torch.randn(k, device=dev).to(torch.bfloat16)
+        flop = 2.0 * PWC_B * 64 * 64 * k * 9 * c
+        t_vfa = bench(lambda: ops.conv2d_act(
+            x, wcl, bias, 1, dil, 'leaky_relu', dilation=dil), args.iters)
+        t_mi = bench(lambda: F.leaky_relu(
+            F.conv2d(xn, wg, bias, 1, dil, dil), 0.1), args.iters)
+        row(f'pwc refiner {c}>{k} 64²', dil, flop, t_vfa, t_mi)
+    print(f'\n{wins}/{total} shapes >= MIOpen')
 
 
 if __name__ == '__main__':

@@ -12,6 +12,21 @@ dispatches through ``ops.pwc_correlation``: ONE fused hand-written CDNA4 HIP
 kernel on GPU (no rearrange pass, LDS-staged center features, wave64
 channel reduction), and a vectorized torch fallback on CPU.  Warping goes
 through ``ops.bilinear_warp``.
+
+Dense-buffer path (``PWCNet.dense_buffer``): each decoder level owns ONE
+zero-initialised channels_last buffer
+
+    [conv5 32 | conv4 64 | conv3 96 | conv2 128 | conv1 128 | corr 81 | f1 |
+     upflow 2 | upfeat 2 | zero pad to a multiple of 8]
+
+which is the channel order the reference's ``cat([new, x], 1)`` chain ends
+with, so the weights need no permutation.  Every dense conv reads the
+suffix behind its own slice and writes its slice in place (fused
+LeakyReLU), the correlation kernel writes its slice directly, and the
+dilated refiner convs run on the same implicit-GEMM kernel: no cat, no
+NCHW conv.  The path is plain ``ops.conv2d_mod`` / ``ops.pwc_correlation``
+calls, so on CPU it is a pure-torch re-expression of the cat path.
+``VFA_NO_PWC_CL=1`` forces the cat path.
 """
 from __future__ import annotations
 
@@ -27,7 +42,7 @@ from .. import ops
 class _ConvLeaky(nn.Sequential):
     """conv + LeakyReLU(0.1) with the Sequential key scheme (``0.weight``)
     preserved; on GPU the pair runs as ONE fused implicit-GEMM kernel
-    (act=leaky_relu) via conv2d_mod — dilated refiner convs fall back."""
+    (act=leaky_relu) via conv2d_mod when the input is channels_last bf16."""
 
     def forward(self, x):
         return ops.conv2d_mod(self[0], x, 'leaky_relu')
@@ -111,6 +126,37 @@ class Decoder(nn.Module):
         flow = self.predict(x)
         return flow, x
 
+    # dense-buffer layout: write offsets of convs[0..4] and of the cost
+    # volume; conv i reads everything behind its own slice
+    DENSE_OFF = [320, 192, 96, 32, 0]
+    CORR_OFF = 448
+
+    def forward_dense(self, f1: torch.Tensor, f2: torch.Tensor,
+                      upflow: Optional[torch.Tensor],
+                      upfeat: Optional[torch.Tensor],
+                      warp_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Same result as ``forward``; the second return value is the
+        level's buffer, of which channels [0, out_channels) are ``x``."""
+        b, fc, h, w = f1.shape
+        width = (self.out_channels + 7) // 8 * 8
+        # allocated per forward (a captured graph replays the allocation)
+        buf = torch.zeros((b, h, w, width), dtype=f1.dtype,
+                          device=f1.device).permute(0, 3, 1, 2)
+        if not self.top:
+            f2 = ops.bilinear_warp(f2, upflow * warp_scale)
+        ops.pwc_correlation(f1, f2, out=buf, out_off=self.CORR_OFF,
+                            act='leaky_relu')
+        if not self.top:
+            o = self.CORR_OFF + 81
+            buf[:, o:o + fc] = f1
+            buf[:, o + fc:o + fc + 2] = upflow
+            buf[:, o + fc + 2:o + fc + 4] = upfeat
+        for conv, off in zip(self.convs, self.DENSE_OFF):
+            ops.conv2d_mod(conv[0], buf, 'leaky_relu', out=buf, out_off=off,
+                           in_off=off + conv[0].out_channels)
+        flow = ops.conv2d_mod(self.predict, buf, in_off=0)
+        return flow, buf
+
 
 class Refiner(nn.Module):
     """Dilated-conv context network (reference pwc_net.py:189-210)."""
@@ -126,14 +172,24 @@ class Refiner(nn.Module):
     def forward(self, x):
         return self.net(x)
 
+    def forward_dense(self, buf: torch.Tensor) -> torch.Tensor:
+        """``buf``: the level-2 decoder buffer, read in place."""
+        x = ops.conv2d_mod(self.net[0][0], buf, 'leaky_relu', in_off=0)
+        for layer in list(self.net)[1:-1]:
+            x = ops.conv2d_mod(layer[0], x, 'leaky_relu')
+        return ops.conv2d_mod(self.net[-1], x)
+
 
 class PWCNet(nn.Module):
     # flow at level l is in level-l pixel units; upsampled flow must be scaled
     # before warping the next level's features (reference pwc_net.py:250-254)
     WARP_SCALES = {5: 0.625, 4: 1.25, 3: 2.5, 2: 5.0}
 
-    def __init__(self):
+    def __init__(self, dense_buffer: Optional[bool] = None):
         super().__init__()
+        # None: automatic (bf16 on GPU with the extension loaded);
+        # True / False force the dense-buffer / the cat path
+        self.dense_buffer = dense_buffer
         self.extractor = PyramidExtractor()
         ch = PyramidExtractor.CHANNELS       # [16, 32, 64, 96, 128, 196]
         self.decoder6 = Decoder(ch[5], top=True)
@@ -142,6 +198,15 @@ class PWCNet(nn.Module):
         self.decoder3 = Decoder(ch[2])
         self.decoder2 = Decoder(ch[1], last=True)
         self.refiner = Refiner(self.decoder2.out_channels)
+
+    def _dense(self, x: torch.Tensor) -> bool:
+        if ops._env_flag('VFA_NO_PWC_CL'):
+            return False
+        if self.dense_buffer is not None:
+            return bool(self.dense_buffer)
+        return (x.is_cuda and x.dtype == torch.bfloat16
+                and ops.hip_available()
+                and not ops._env_flag('VFA_FORCE_TORCH_OPS'))
 
     def forward(self, im1: torch.Tensor, im2: torch.Tensor) -> torch.Tensor:
         """uint8-range RGB (B, 3, H, W) pairs → (B, 2, H, W) flow in input
@@ -157,19 +222,26 @@ class PWCNet(nn.Module):
             im2 = F.interpolate(im2, (h64, w64), mode='bilinear', align_corners=False)
         p1 = self.extractor(im1)
         p2 = self.extractor(im2)
+        # dense: each decoder returns its level buffer, whose leading
+        # out_channels are the cat path's feature tensor
+        dense = self._dense(p1[0])
+        decs = {6: self.decoder6, 5: self.decoder5, 4: self.decoder4,
+                3: self.decoder3, 2: self.decoder2}
+
+        def run(dec, *args):
+            return dec.forward_dense(*args) if dense else dec(*args)
+
         # pyramid list index: level l features are p[l-1] (1/2^l resolution)
-        flow6, feat6 = self.decoder6(p1[5], p2[5], None, None, 0.0)
-        flow, feat = flow6, feat6
-        dec = {5: self.decoder5, 4: self.decoder4, 3: self.decoder3,
-               2: self.decoder2}
+        flow, feat = run(self.decoder6, p1[5], p2[5], None, None, 0.0)
         for lvl in (5, 4, 3, 2):
-            prev_dec = {6: self.decoder6, 5: self.decoder5, 4: self.decoder4,
-                        3: self.decoder3}[lvl + 1]
+            prev_dec = decs[lvl + 1]
             upflow = prev_dec.upflow(flow)
-            upfeat = prev_dec.upfeat(feat)
-            flow, feat = dec[lvl](p1[lvl - 1], p2[lvl - 1], upflow, upfeat,
-                                  self.WARP_SCALES[lvl])
-        flow = flow + self.refiner(feat)
+            upfeat = prev_dec.upfeat(
+                feat[:, :prev_dec.out_channels] if dense else feat)
+            flow, feat = run(decs[lvl], p1[lvl - 1], p2[lvl - 1], upflow,
+                             upfeat, self.WARP_SCALES[lvl])
+        flow = flow + (self.refiner.forward_dense(feat) if dense
+                       else self.refiner(feat))
         # ×20 to pixel units at 1/4 res, then resize to the input resolution
         flow = F.interpolate(flow * 20.0, (h, w), mode='bilinear',
                              align_corners=False)

@@ -178,17 +178,40 @@ def mhsa_fused(qkv: torch.Tensor, heads: int,
 
 # ---------------------------------------------------------------- flow ops
 def pwc_correlation(f1: torch.Tensor, f2: torch.Tensor,
-                    max_disp: int = 4) -> torch.Tensor:
+                    max_disp: int = 4, out: Optional[torch.Tensor] = None,
+                    out_off: int = 0, act: str = 'none') -> torch.Tensor:
     """PWC cost volume: (B, C, H, W) × 2 → (B, (2*max_disp+1)^2, H, W).
 
     Channel-mean dot products over a (2d+1)^2 displacement window of f2
     (reference vendors this as 4 CuPy CUDA kernels,
     models/pwc/pwc_src/correlation.py; here it is ONE fused CDNA4 kernel on
     GPU and a vectorized torch implementation on CPU).
+
+    ``act`` is 'none' or 'leaky_relu' (slope 0.1), applied to the cost
+    volume.  With ``out`` (B, >= out_off + 81, H, W) the result goes into
+    its channels [out_off, out_off + 81) and ``out`` is returned; on GPU
+    ``out`` is a channels_last bf16 buffer and the kernels store the slice
+    themselves (no f32 NCHW tensor, cast or copy).
     """
+    if act not in ('none', 'leaky_relu'):
+        raise ValueError(f'pwc_correlation: unsupported act {act!r}')
+    leaky = act == 'leaky_relu'
     if _use_hip(f1):
-        return _ext.pwc_correlation(f1.contiguous(), f2.contiguous(), max_disp)
-    return _pwc_correlation_torch(f1, f2, max_disp)
+        direct = out is None or (
+            out.dtype == torch.bfloat16
+            and out.is_contiguous(memory_format=torch.channels_last))
+        y = _ext.pwc_correlation(f1.contiguous(), f2.contiguous(), max_disp,
+                                 out if direct else None, out_off, leaky)
+        if direct:
+            return y
+    else:
+        y = _pwc_correlation_torch(f1, f2, max_disp)
+        if leaky:
+            y = torch.nn.functional.leaky_relu(y, 0.1)
+    if out is not None:
+        out[:, out_off:out_off + y.shape[1]] = y
+        return out
+    return y
 
 
 def _pwc_correlation_torch(f1: torch.Tensor, f2: torch.Tensor,
@@ -544,7 +567,8 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
                stride=1, padding=0, act: str = 'none',
                res: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None,
-               out_off: int = 0) -> torch.Tensor:
+               out_off: int = 0, dilation=1, in_off: int = 0,
+               in_ch: Optional[int] = None) -> torch.Tensor:
     """Fused conv2d + bias + activation (+ residual) on channels_last bf16.
 
     GPU path: the in-tree implicit-GEMM MFMA kernel (conv2d.hip) — the
@@ -553,8 +577,22 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
     conv stacks at models/raft/raft_src/extractor.py:118-192,
     models/i3d/i3d_src/i3d_net.py:37-105).  CPU / unsupported shapes:
     F.conv2d composition.
+
+    ``dilation`` is an int or a pair.  ``in_ch`` makes ``x`` a wider buffer
+    of which the conv reads channels [in_off, in_off + in_ch); the kernel
+    reads the slice in place (in_off, in_ch and the buffer width multiples
+    of 8).  ``out`` / ``out_off`` write a channel slice of a wider buffer,
+    which may be ``x`` itself when the two slices are disjoint: the
+    cat-free DenseNet step ``x = cat([conv(x), x], 1)``.
     """
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
+    dh, dw = (dilation, dilation) if isinstance(dilation, int) else dilation
+    if in_ch is None:
+        if in_off:
+            raise ValueError('conv2d_act: in_off needs in_ch')
+        cx = x.shape[1]
+    else:
+        cx = in_ch
     if isinstance(padding, int):
         pt = pb = pl = pr = padding
     elif len(padding) == 2:
@@ -566,12 +604,15 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
     # caller pads the weight; the kernel's pad pass widens the input)
     if (_use_hip(x) and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16
-            and weight.shape[1] == (x.shape[1] + 7) // 8 * 8
+            and weight.shape[1] == (cx + 7) // 8 * 8
+            and (in_ch is None or (in_ch % 8 == 0 and in_off % 8 == 0
+                                   and x.shape[1] % 8 == 0))
             and x.is_contiguous(memory_format=torch.channels_last)
             and not _env_flag('VFA_NO_CONV')):
         if (weight.shape[2] == 1 and weight.shape[3] == 1
                 and (sh, sw) == (1, 1) and (pt, pb, pl, pr) == (0, 0, 0, 0)
                 and weight.shape[1] == x.shape[1] and out is None
+                and in_ch is None
                 and weight.shape[0] % 8 == 0):
             # pure 1x1: the linear stack's router picks the right GEMM
             # structure — in particular the thin-K streaming kernel for
@@ -582,7 +623,10 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
         r = res.contiguous(memory_format=torch.channels_last) \
             if res is not None else None
         return _ext.conv2d_nhwc(x, w_cl, bias, r, sh, sw, pt, pb, pl, pr,
-                                _act_id(act), out, out_off)
+                                _act_id(act), out, out_off, dh, dw, in_off,
+                                0 if in_ch is None else in_ch)
+    if in_ch is not None:
+        x = x[:, in_off:in_off + in_ch]
     if weight.shape[1] > x.shape[1]:
         # caller passed a channel-padded weight but the GPU path declined
         # (VFA_NO_CONV, forced torch ops, ...): slice the zero pad back off
@@ -590,9 +634,11 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
     if pt != pb or pl != pr:
         x = torch.nn.functional.pad(x, (pl, pr, pt, pb))
         pt = pl = 0
-        y = torch.nn.functional.conv2d(x, weight, bias, (sh, sw), 0)
+        y = torch.nn.functional.conv2d(x, weight, bias, (sh, sw), 0,
+                                       (dh, dw))
     else:
-        y = torch.nn.functional.conv2d(x, weight, bias, (sh, sw), (pt, pl))
+        y = torch.nn.functional.conv2d(x, weight, bias, (sh, sw), (pt, pl),
+                                       (dh, dw))
     if res is not None:
         y = y + res
     y = _apply_act(y, act)
@@ -603,61 +649,93 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
 
 
 def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
-               res: Optional[torch.Tensor] = None) -> torch.Tensor:
+               res: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, out_off: int = 0,
+               in_off: Optional[int] = None) -> torch.Tensor:
     """Route an ``nn.Conv2d`` module call through the in-tree kernels:
     1x1 → fused MFMA GEMM (conv1x1_act), kxk → implicit-GEMM conv
-    (conv2d_act); eager composition otherwise (CPU, C % 8 != 0, dilation,
-    groups, tiny K_out)."""
+    (conv2d_act, dilation included); eager composition otherwise (CPU,
+    groups, tiny K_out with C % 8 != 0).
+
+    ``out`` / ``out_off``: write the result into channels
+    [out_off, out_off + K_out) of the wider buffer ``out`` and return it.
+
+    ``in_off``: ``x`` is a wide buffer and the conv reads
+    ``conv.in_channels`` channels starting at ``in_off``.  On the kernel
+    path the slice width is ``conv.in_channels`` rounded up to a multiple
+    of 8 and the cached weight is zero-padded to that width, so the
+    channels the rounding adds must exist in the buffer and be finite: the
+    zero weight columns cancel them.  ``out`` may be ``x`` when the read
+    and written slices are disjoint."""
     w = conv.weight
     kh, kw = w.shape[2], w.shape[3]
-    c = x.shape[1]
+    sliced = in_off is not None
+    c = conv.in_channels if sliced else x.shape[1]
+    c8 = (c + 7) // 8 * 8
     eligible = (x.is_cuda and x.dtype == torch.bfloat16
                 and w.dtype == torch.bfloat16
-                and conv.dilation == (1, 1) and conv.groups == 1
+                and conv.groups == 1
                 and x.is_contiguous(memory_format=torch.channels_last)
                 and hip_available() and not _env_flag('VFA_NO_CONV')
                 and not _env_flag('VFA_FORCE_TORCH_OPS'))
+    if eligible and sliced:
+        if in_off % 8 or x.shape[1] % 8 or in_off + c8 > x.shape[1]:
+            raise ValueError(
+                f'conv2d_mod: slice [{in_off}, {in_off + c8}) of a '
+                f'{x.shape[1]}-channel buffer needs in_off and the buffer '
+                'width to be multiples of 8 and the rounded slice inside it')
+    kw_slice = dict(in_off=in_off, in_ch=c8) if sliced else {}
+    key = (w._version, w.dtype, w.device, w.data_ptr())
     if eligible and w.shape[0] < 16 and res is None:
         # tiny-N heads (RAFT flow head N=2, per GRU iteration): pad the
         # OUTPUT channels to 16 (cached, weight-version-keyed), run
-        # in-tree, slice back
+        # in-tree, slice back.  A slice input also gets its input channels
+        # padded to the slice width.
         kout = w.shape[0]
-        key = (w._version, w.dtype, w.device, w.data_ptr())
+        cpad = c8 - c if sliced else 0
+        key = key + (cpad,)
         ent = getattr(conv, '_vfa_wnpad', None)
         if ent is None or ent[0] != key:
             wp = torch.nn.functional.pad(
-                w, (0, 0, 0, 0, 0, 0, 0, 16 - kout)).contiguous(
+                w, (0, 0, 0, 0, 0, cpad, 0, 16 - kout)).contiguous(
                     memory_format=torch.channels_last)
             bp = (torch.nn.functional.pad(conv.bias, (0, 16 - kout))
                   if conv.bias is not None else None)
             conv._vfa_wnpad = ent = (key, wp, bp)
-        y = conv2d_act(x, ent[1], ent[2], conv.stride, conv.padding, act)
+        y = conv2d_act(x, ent[1], ent[2], conv.stride, conv.padding, act,
+                       dilation=conv.dilation, **kw_slice)
+        if out is not None:
+            out[:, out_off:out_off + kout] = y[:, :kout]
+            return out
         return y[:, :kout].contiguous(memory_format=torch.channels_last)
     if eligible and c % 8 != 0:
         # stems (C=3/2/1) and the RAFT corr input (C=324): zero-pad the
         # channel dim — weight padded once and cached on the module (keyed
         # on the weight VERSION so a later load_state_dict invalidates),
-        # input padded inside the conv's (fused) pad pass
-        key = (w._version, w.dtype, w.device, w.data_ptr())
+        # input padded inside the conv's (fused) pad pass; a slice input is
+        # read in place at the padded width instead
         ent = getattr(conv, '_vfa_wpad', None)
         if ent is None or ent[0] != key:
-            c8 = (c + 7) // 8 * 8
             wp = torch.nn.functional.pad(
                 w, (0, 0, 0, 0, 0, c8 - c)).contiguous(
                     memory_format=torch.channels_last)
             conv._vfa_wpad = ent = (key, wp)
         return conv2d_act(x, ent[1], conv.bias, conv.stride, conv.padding,
-                          act, res)
+                          act, res, out, out_off, conv.dilation, **kw_slice)
     if eligible and kh == 1 and kw == 1 and conv.stride == (1, 1) \
-            and w.shape[0] % 8 == 0:
+            and w.shape[0] % 8 == 0 and not sliced and out is None:
         return conv1x1_act(x, w, conv.bias, act, res)
     if eligible:
         return conv2d_act(x, w, conv.bias, conv.stride, conv.padding, act,
-                          res)
-    y = conv(x)
+                          res, out, out_off, conv.dilation, **kw_slice)
+    y = conv(x[:, in_off:in_off + c] if sliced else x)
     if res is not None:
         y = y + res
-    return _apply_act(y, act)
+    y = _apply_act(y, act)
+    if out is not None:
+        out[:, out_off:out_off + y.shape[1]] = y
+        return out
+    return y
 
 
 def grid_sample_bilinear(x: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:

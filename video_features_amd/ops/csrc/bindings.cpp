@@ -20,7 +20,7 @@ void vfa_grid_sample(const void*, const void*, void*, long long, int, int,
 void vfa_corr_repack(const void*, void*, int, int, int, int, int,
                      hipStream_t);
 void vfa_pwc_correlation(const void*, const void*, const void*, void*, int,
-                         int, int, int, int, hipStream_t);
+                         int, int, int, int, int, int, hipStream_t);
 void vfa_mhsa_small(const void*, const void*, const void*, void*, int, int,
                     int, float, int, hipStream_t);
 void vfa_flash_qkv(const void*, void*, int, int, int, float, hipStream_t);
@@ -53,7 +53,8 @@ void vfa_temporal_merge(const void*, void*, int, int, int, int, int, int,
                         int, long long, int, int, hipStream_t);
 void vfa_conv2d_nhwc(const void*, const void*, const void*, const void*,
                      const void*, void*, int, int, int, int, int, int, int,
-                     int, int, int, int, int, int, int, int, hipStream_t);
+                     int, int, int, int, int, int, int, int, int, int, int,
+                     hipStream_t);
 void vfa_conv2d_pick_tile(int, int, int*, int*);
 void vfa_pad2d_nhwc(const void*, void*, int, int, int, int, int, int, int,
                     int, int, hipStream_t);
@@ -164,7 +165,12 @@ torch::Tensor grid_sample_bilinear(torch::Tensor x, torch::Tensor coords) {
 }
 
 torch::Tensor pwc_correlation(torch::Tensor f1, torch::Tensor f2,
-                              int64_t max_disp) {
+                              int64_t max_disp,
+                              c10::optional<torch::Tensor> out_buf,
+                              int64_t out_off, bool leaky) {
+  // out_buf: a (B, >= out_off + 81, H, W) channels_last bf16 buffer; the
+  // kernels write the cost volume (LeakyReLU(0.1) of it when leaky) into
+  // its channels [out_off, out_off + 81) and nothing else
   TORCH_CHECK(f1.is_cuda() && f1.is_contiguous() && f2.is_contiguous());
   TORCH_CHECK(max_disp == 4, "kernel is specialized for max_disp=4");
   TORCH_CHECK(f1.sizes() == f2.sizes());
@@ -180,9 +186,24 @@ torch::Tensor pwc_correlation(torch::Tensor f1, torch::Tensor f2,
   // tiled path (c<=64) reads f1 as NCHW directly; wave path needs both packed
   if (c > 64) vfa_corr_repack(f1.data_ptr(), f1p.data_ptr(), b, c, h, w, tag, stream);
   vfa_corr_repack(f2.data_ptr(), f2p.data_ptr(), b, c, h, w, tag, stream);
+  if (out_buf.has_value()) {
+    auto out = *out_buf;
+    TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
+                out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
+                out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
+                out.size(2) == h && out.size(3) == w && out_off >= 0 &&
+                out_off + 81 <= out.size(1),
+                "out buffer must be CL bf16 (B, >=off+81, H, W)");
+    vfa_pwc_correlation(f1.data_ptr(), f1p.data_ptr(), f2p.data_ptr(),
+                        static_cast<char*>(out.data_ptr()) + out_off * 2, b,
+                        c, h, w, tag, (int)out.size(1), leaky ? 1 : 0,
+                        stream);
+    return out;
+  }
   auto out = torch::empty({b, 81, h, w}, opts.dtype(torch::kFloat32));
   vfa_pwc_correlation(f1.data_ptr(), f1p.data_ptr(), f2p.data_ptr(),
-                      out.data_ptr(), b, c, h, w, tag, stream);
+                      out.data_ptr(), b, c, h, w, tag, 0, leaky ? 1 : 0,
+                      stream);
   return out.to(f1.scalar_type());
 }
 
@@ -464,17 +485,32 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
                           int64_t pt, int64_t pb, int64_t pl, int64_t pr,
                           int64_t act,
                           c10::optional<torch::Tensor> out_buf,
-                          int64_t out_off) {
+                          int64_t out_off, int64_t dil_h, int64_t dil_w,
+                          int64_t in_off, int64_t in_ch) {
   // x (B, C, H, W) channels_last bf16; w (K, C, KH, KW) channels_last bf16
   // (physical (K, KH, KW, C) = the (N, Kr) B-operand); out (B, K, OH, OW)
   // channels_last.  Implicit-GEMM MFMA kernel; input pre-padded by the
-  // pad2d kernel when pad > 0.
+  // pad2d kernel when C % 8 != 0.
+  // in_ch > 0: x is a wider buffer and the conv reads its channels
+  // [in_off, in_off + in_ch) in place (pixel stride ldx = x.size(1)).
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && cl_contig(x),
               "x must be channels_last");
   TORCH_CHECK(w.dim() == 4 && cl_contig(w), "w must be channels_last");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
               w.scalar_type() == torch::kBFloat16);
-  const int b = (int)x.size(0), c = (int)x.size(1);
+  const bool slice = in_ch > 0;
+  const int xc = (int)x.size(1);
+  if (slice) {
+    // each lane's 16-B load must stay aligned and inside one tap
+    TORCH_CHECK(in_off >= 0 && in_off % 8 == 0 && in_ch % 8 == 0 &&
+                xc % 8 == 0 && in_off + in_ch <= xc,
+                "slice input needs in_off, in_ch and the buffer width to be "
+                "multiples of 8 and the slice inside the buffer");
+  } else {
+    TORCH_CHECK(in_off == 0 && in_ch == 0, "in_off needs in_ch > 0");
+  }
+  TORCH_CHECK(dil_h >= 1 && dil_w >= 1 && stride_h >= 1 && stride_w >= 1);
+  const int b = (int)x.size(0), c = slice ? (int)in_ch : xc;
   const int h = (int)x.size(2), ww = (int)x.size(3);
   const int kout = (int)w.size(0), kh = (int)w.size(2), kw = (int)w.size(3);
   // C % 8 != 0 (stems, the RAFT corr input): the pad pass widens the
@@ -483,8 +519,10 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
   const int c8 = (c + 7) / 8 * 8;
   TORCH_CHECK(w.size(1) == c8, "weight C must be input C padded up to 8");
   const int hp = h + (int)(pt + pb), wp = ww + (int)(pl + pr);
-  const int oh = (hp - kh) / (int)stride_h + 1;
-  const int ow = (wp - kw) / (int)stride_w + 1;
+  const int ekh = (int)dil_h * (kh - 1) + 1, ekw = (int)dil_w * (kw - 1) + 1;
+  TORCH_CHECK(hp >= ekh && wp >= ekw, "dilated filter larger than the input");
+  const int oh = (hp - ekh) / (int)stride_h + 1;
+  const int ow = (wp - ekw) / (int)stride_w + 1;
   auto stream = current_stream();
   // C % 8 == 0: the kernel zero-pads inline (validity check + zero-page
   // redirect in the A staging) — no materialized pad pass.  Channel
@@ -540,21 +578,34 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
                 "out buffer must be CL bf16 (B, >=off+kout, OH, OW)");
     ldc = (int)out.size(1);
     optr = static_cast<char*>(out.data_ptr()) + out_off * 2;
+    // x and out may be ONE buffer (the in-place dense step) when the read
+    // and written channel slices are disjoint; any other overlap of the two
+    // memories is refused before anything is launched
+    const char* xb = static_cast<const char*>(x.data_ptr());
+    const char* ob = static_cast<const char*>(out.data_ptr());
+    if (xb < ob + out.numel() * 2 && ob < xb + x.numel() * 2) {
+      TORCH_CHECK(xb == ob && x.sizes() == out.sizes() &&
+                  (in_off + c <= out_off || out_off + kout <= in_off),
+                  "conv2d_nhwc: the read and written channel slices of one "
+                  "buffer overlap");
+    }
   } else {
     out = torch::empty({(long)b, oh, ow, kout}, x.options())
               .permute({0, 3, 1, 2});
     optr = out.data_ptr();
   }
   if (inline_pad)
-    vfa_conv2d_nhwc(xp.data_ptr(), w.data_ptr(), bptr, rptr,
+    vfa_conv2d_nhwc(static_cast<const char*>(xp.data_ptr()) + in_off * 2,
+                    w.data_ptr(), bptr, rptr,
                     zpage.data_ptr(), optr, b, h, ww, c8, oh, ow,
                     kout, kh, kw, (int)stride_h, (int)stride_w, (int)pt,
-                    (int)pl, ldc, (int)act, stream);
+                    (int)pl, ldc, (int)act, (int)dil_h, (int)dil_w,
+                    slice ? xc : c8, stream);
   else
     vfa_conv2d_nhwc(xp.data_ptr(), w.data_ptr(), bptr, rptr,
                     zpage.data_ptr(), optr, b, hp, wp, c8, oh,
                     ow, kout, kh, kw, (int)stride_h, (int)stride_w, 0, 0,
-                    ldc, (int)act, stream);
+                    ldc, (int)act, (int)dil_h, (int)dil_w, c8, stream);
   return out;
 }
 

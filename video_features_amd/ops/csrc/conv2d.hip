@@ -25,6 +25,18 @@
 // operand's im2col staging, the guarded W staging, the K loop around the
 // shared K-step, the pad pass and the tile choice.  Requires C % 8 == 0
 // (each lane's 16-B segment stays inside one tap).
+//
+// Dilation (dh, dw) moves tap (r, s) to (y0 + r*dh, x0 + s*dw).  The input
+// pixel stride ldx may exceed C: the conv then reads a C-wide channel slice
+// of a wider NHWC buffer (the host folds the slice's channel offset into
+// the x pointer), element address  base + (iy*Wp + ix)*ldx + c  with
+// base = b*Hp*Wp*ldx.  ldx % 8 == 0 and a slice offset % 8 == 0 keep every
+// 16-B segment aligned.  dh = dw = 1, ldx = C is the plain conv: its
+// kernels are the GEN = false instantiations, where the three values are
+// compile-time 1, 1 and cin, so the hot shapes run the code they ran before
+// dilation existed (with the three values as run-time fields two hot shapes
+// measured 0.6% and 1% behind the previous build, at or above the spread
+// of its own two runs; profiles/pwc_decoder.md).
 #include "mfma_tile.h"
 
 // the one copy of the tile choice (defined below; also bound to Python as
@@ -44,18 +56,26 @@ struct ConvGeom {
   int kr;                   // KH*KW*C
 };
 
+// tap / pixel addressing beyond the plain conv
+struct ConvAddr {
+  int dh, dw;               // dilation
+  int ldx;                  // input pixel stride in elements (>= cin; cin
+                            // stays the width the K index runs over)
+};
+
 // decompose output-pixel index m -> (image base, receptive-field origin)
 struct PixRef {
-  long long base;           // bi * H * W * C
+  long long base;           // bi * H * W * ldx
   int y0, x0;               // oy*sh - pt, ox*sw - pl (may be negative)
 };
 
-__device__ __forceinline__ PixRef pix_ref(const ConvGeom& g, int m) {
+__device__ __forceinline__ PixRef pix_ref(const ConvGeom& g,
+                                          const ConvAddr& a, int m) {
   const int ox = m % g.ow;
   const int t = m / g.ow;
   const int oy = t % g.oh;
   const int bi = t / g.oh;
-  return PixRef{(long long)bi * g.hp * g.wp * g.cin,
+  return PixRef{(long long)bi * g.hp * g.wp * a.ldx,
                 oy * g.sh - g.pt, ox * g.sw - g.pl};
 }
 
@@ -67,8 +87,8 @@ __device__ __forceinline__ PixRef pix_ref(const ConvGeom& g, int m) {
 template <int ROWS, int WAVES>
 __device__ __forceinline__ void conv_stage_a(
     const __bf16* __restrict__ x, const __bf16* __restrict__ zp,
-    const ConvGeom& g, const PixRef* __restrict__ aref, int k0,
-    char* lds_base, int wave, int lane, int kfrac0, int arin_half,
+    const ConvGeom& g, const ConvAddr& a, const PixRef* __restrict__ aref,
+    int k0, char* lds_base, int wave, int lane, int kfrac0, int arin_half,
     int piece, int npieces) {
   constexpr int NSUB = ROWS * 128 / 1024;
   constexpr int PER_WAVE = NSUB / WAVES;
@@ -83,11 +103,11 @@ __device__ __forceinline__ void conv_stage_a(
     const int c = k - tap * g.cin;
     const int r = tap / g.kw;
     const int s = tap - r * g.kw;
-    const int iy = aref[i].y0 + r, ix = aref[i].x0 + s;
+    const int iy = aref[i].y0 + r * a.dh, ix = aref[i].x0 + s * a.dw;
     const bool ok = (unsigned)iy < (unsigned)g.hp &&
                     (unsigned)ix < (unsigned)g.wp;
     const __bf16* src =
-        ok ? x + aref[i].base + ((long long)iy * g.wp + ix) * g.cin + c
+        ok ? x + aref[i].base + ((long long)iy * g.wp + ix) * a.ldx + c
            : zp + (lane & 63) * 8;
     __builtin_amdgcn_global_load_lds(
         reinterpret_cast<const unsigned int*>(src),
@@ -99,23 +119,23 @@ __device__ __forceinline__ void conv_stage_a(
 // same LDS image, zero fill (covers out-of-image taps too).
 template <int ROWS, int THREADS>
 __device__ __forceinline__ void conv_guard_a(
-    const __bf16* __restrict__ x, const ConvGeom& g, int m0, int mtotal,
-    int k0, char* lds_base, int tid) {
+    const __bf16* __restrict__ x, const ConvGeom& g, const ConvAddr& a,
+    int m0, int mtotal, int k0, char* lds_base, int tid) {
   for (int t = tid; t < ROWS * 8; t += THREADS) {  // 8 16-B segs per row
     const int row = t >> 3, seg = t & 7;
     uint4 v = {0u, 0u, 0u, 0u};
     const int m = m0 + row;
     const int k = k0 + seg * 8;
     if (m < mtotal && k < g.kr) {
-      const PixRef pr = pix_ref(g, m);
+      const PixRef pr = pix_ref(g, a, m);
       const int tap = k / g.cin;
       const int c = k - tap * g.cin;
       const int r = tap / g.kw;
       const int s = tap - r * g.kw;
-      const int iy = pr.y0 + r, ix = pr.x0 + s;
+      const int iy = pr.y0 + r * a.dh, ix = pr.x0 + s * a.dw;
       if ((unsigned)iy < (unsigned)g.hp && (unsigned)ix < (unsigned)g.wp)
         v = *reinterpret_cast<const uint4*>(
-            x + pr.base + ((long long)iy * g.wp + ix) * g.cin + c);
+            x + pr.base + ((long long)iy * g.wp + ix) * a.ldx + c);
     }
     *reinterpret_cast<uint4*>(lds_base + swz(row * 128 + seg * 16)) = v;
   }
@@ -142,8 +162,9 @@ __device__ __forceinline__ void conv_guard_w(
 
 // Tile variants: 256x256 (8 waves, 2Mx4N), 128x128 (4 waves, 2x2),
 // 256x64 (4 waves, 4Mx1N — for K_out = 64/192 nets where a 128-wide N
-// tile is half empty).
-template <int ACT, int BM, int BN, int WAVES, int WN>
+// tile is half empty).  GEN: dilation and the input pixel stride come from
+// the trailing arguments; otherwise they are 1, 1 and cin.
+template <int ACT, int BM, int BN, int WAVES, int WN, bool GEN>
 __global__ __launch_bounds__(WAVES * 64)
 void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
                         const __bf16* __restrict__ wgt,
@@ -151,7 +172,9 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
                         const __bf16* __restrict__ res,
                         const __bf16* __restrict__ zp,
                         __bf16* __restrict__ out, ConvGeom g, int mtotal,
-                        int ldc, int tiles_m, int tiles_n) {
+                        int ldc, int tiles_m, int tiles_n, int dh, int dw,
+                        int ldx) {
+  const ConvAddr a = GEN ? ConvAddr{dh, dw, ldx} : ConvAddr{1, 1, g.cin};
   constexpr int MI = BM / (WAVES / WN) / 16;   // 16-row MFMA tiles / wave
   constexpr int NJ = BN / WN / 16;             // 16-col MFMA tiles / wave
   constexpr int TILE_A = BM * BK * 2, TILE_B = BN * BK * 2;
@@ -184,18 +207,19 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
   for (int i = 0; i < PER_WAVE; ++i) {
     const int sub = wave * PER_WAVE + i;
     const int m = m0 + sub * 8 + a_rin;
-    aref[i] = pix_ref(g, m < mtotal ? m : mtotal - 1);
+    aref[i] = pix_ref(g, a, m < mtotal ? m : mtotal - 1);
   }
 
   auto stage = [&](int buf, int kt) {
     const int k0 = kt * BK;
     if (tile_full && (kfull || kt + 1 < nk)) {
-      conv_stage_a<BM, WAVES>(x, zp, g, aref, k0, sA(buf), wave, lane,
+      conv_stage_a<BM, WAVES>(x, zp, g, a, aref, k0, sA(buf), wave, lane,
                               kfrac0, a_rin >> 1, -1, 1);
       stage_glds<BN, WAVES>(wgt + (long long)n0 * kr + k0, kr, sB(buf),
                             wave, lane);
     } else {
-      conv_guard_a<BM, THREADS>(x, g, m0, mtotal, k0, sA(buf), threadIdx.x);
+      conv_guard_a<BM, THREADS>(x, g, a, m0, mtotal, k0, sA(buf),
+                                threadIdx.x);
       conv_guard_w<BN, THREADS>(wgt + (long long)n0 * kr + k0, kr, n0, n,
                                 k0, kr, sB(buf), threadIdx.x);
     }
@@ -221,8 +245,8 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
       mfma_kstep<MI, NJ>(sA(cur), sB(cur), wm * (MI * 16), wn * (NJ * 16),
                          kk, lane, acc, [&] {
         if (glds_nxt) {
-          conv_stage_a<BM, WAVES>(x, zp, g, aref, k0_nxt, sA(1 - cur), wave,
-                                  lane, kfrac0, a_rin >> 1, kk, 2);
+          conv_stage_a<BM, WAVES>(x, zp, g, a, aref, k0_nxt, sA(1 - cur),
+                                  wave, lane, kfrac0, a_rin >> 1, kk, 2);
           stage_glds_piece<BN, WAVES>(wgt + (long long)n0 * kr + k0_nxt, kr,
                                       sB(1 - cur), wave, lane, kk, 2);
         }
@@ -240,30 +264,42 @@ void conv2d_nhwc_kernel(const __bf16* __restrict__ x,
 template <int ACT, int BM, int BN, int WAVES, int WN>
 void launch_cfg(const void* x, const void* w, const void* bias,
                 const void* res, const void* zp, void* out,
-                const ConvGeom& g, int m, int ldc, hipStream_t stream) {
+                const ConvGeom& g, const ConvAddr& a, int m, int ldc,
+                hipStream_t stream) {
   const int tiles_m = (m + BM - 1) / BM, tiles_n = (g.kout + BN - 1) / BN;
   const dim3 grid(tiles_m * tiles_n);
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
-  hipLaunchKernelGGL((conv2d_nhwc_kernel<ACT, BM, BN, WAVES, WN>), grid,
-                     dim3(WAVES * 64), lds, stream, (const __bf16*)x,
-                     (const __bf16*)w, (const __bf16*)bias,
-                     (const __bf16*)res, (const __bf16*)zp, (__bf16*)out,
-                     g, m, ldc, tiles_m, tiles_n);
+  auto launch = [&](auto gen) {
+    hipLaunchKernelGGL(
+        (conv2d_nhwc_kernel<ACT, BM, BN, WAVES, WN, decltype(gen)::value>),
+        grid, dim3(WAVES * 64), lds, stream, (const __bf16*)x,
+        (const __bf16*)w, (const __bf16*)bias, (const __bf16*)res,
+        (const __bf16*)zp, (__bf16*)out, g, m, ldc, tiles_m, tiles_n, a.dh,
+        a.dw, a.ldx);
+  };
+  if (a.dh == 1 && a.dw == 1 && a.ldx == g.cin)
+    launch(std::false_type{});
+  else
+    launch(std::true_type{});
 }
 
 template <int ACT>
 void launch_conv(const void* x, const void* w, const void* bias,
                  const void* res, const void* zp, void* out,
-                 const ConvGeom& g, int ldc, hipStream_t stream) {
+                 const ConvGeom& g, const ConvAddr& a, int ldc,
+                 hipStream_t stream) {
   const int m = g.b * g.oh * g.ow;
   int bm, bn;
   vfa_conv2d_pick_tile(m, g.kout, &bm, &bn);
   if (bm == 256 && bn == 256)
-    launch_cfg<ACT, 256, 256, 8, 4>(x, w, bias, res, zp, out, g, m, ldc, stream);
+    launch_cfg<ACT, 256, 256, 8, 4>(x, w, bias, res, zp, out, g, a, m, ldc,
+                                   stream);
   else if (bm == 256)
-    launch_cfg<ACT, 256, 64, 4, 1>(x, w, bias, res, zp, out, g, m, ldc, stream);
+    launch_cfg<ACT, 256, 64, 4, 1>(x, w, bias, res, zp, out, g, a, m, ldc,
+                                   stream);
   else
-    launch_cfg<ACT, 128, 128, 4, 2>(x, w, bias, res, zp, out, g, m, ldc, stream);
+    launch_cfg<ACT, 128, 128, 4, 2>(x, w, bias, res, zp, out, g, a, m, ldc,
+                                   stream);
 }
 
 // ------------------------------------------------------------- pad kernel
@@ -336,15 +372,19 @@ void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn) {
 // pass 0 with pre-padded h/w when the pad was materialized
 // ldc: output row stride in elements (= kout normally; larger when the
 // epilogue writes a channel slice of a wider NHWC buffer)
+// dh/dw: dilation.  ldx: input pixel stride in elements (= cin normally;
+// larger when x points at a channel slice of a wider NHWC buffer)
 void vfa_conv2d_nhwc(const void* x, const void* w, const void* bias,
                      const void* res, const void* zp, void* out, int b,
                      int hp, int wp, int cin, int oh, int ow, int kout,
                      int kh, int kw, int sh, int sw, int pt, int pl,
-                     int ldc, int act, hipStream_t stream) {
+                     int ldc, int act, int dh, int dw, int ldx,
+                     hipStream_t stream) {
   ConvGeom g{b, hp, wp, cin, oh, ow, kout, kh, kw, sh, sw, pt, pl,
              kh * kw * cin};
+  const ConvAddr a{dh, dw, ldx};
   dispatch_act(act, [&](auto id) {
-    launch_conv<decltype(id)::value>(x, w, bias, res, zp, out, g, ldc,
+    launch_conv<decltype(id)::value>(x, w, bias, res, zp, out, g, a, ldc,
                                      stream);
   });
 }

@@ -16,13 +16,30 @@
 //    wave shuffle reduction per displacement.
 //
 // Output (B, (2d+1)^2, H, W) = channel-MEAN dot products (reference
-// semantics).
+// semantics), float32 NCHW.  With ldo > 0 the kernels instead write bf16
+// into the channel slice [out_off, out_off + 81) of an NHWC buffer whose
+// pixel stride is ldo elements (the host folds out_off into the pointer):
+// the PWC decoder's dense buffer, no NCHW tensor, cast or cat in between.
+// leaky != 0 applies LeakyReLU(0.1) before the store in either mode.
 #include "vfa_common.h"
 
 namespace {
 
 constexpr int MAXD = 4;           // displacement radius (9x9 window)
 constexpr int NDISP = 81;
+
+// one cost-volume value: displacement d of pixel pix (= y*w + x) of image bi
+__device__ __forceinline__ void corr_store(void* __restrict__ out, int bi,
+                                           long long pix, int d,
+                                           long long hw, int ldo, int leaky,
+                                           float v) {
+  if (leaky && v < 0.f) v *= 0.1f;
+  if (ldo > 0)
+    static_cast<__hip_bfloat16*>(out)[((long long)bi * hw + pix) * ldo + d] =
+        from_f32<__hip_bfloat16>(v);
+  else
+    static_cast<float*>(out)[((long long)bi * NDISP + d) * hw + pix] = v;
+}
 
 // ---------------------------------------------------------------- repack
 template <typename T>
@@ -51,8 +68,8 @@ __global__ void repack_kernel(const T* __restrict__ in, T* __restrict__ out,
 template <typename T>
 __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
                                   const T* __restrict__ f2p,  // padded NHWC
-                                  float* __restrict__ out, int b, int c,
-                                  int h, int w) {
+                                  void* __restrict__ out, int b, int c,
+                                  int h, int w, int ldo, int leaky) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cp = c + 1;   // +1 element pad breaks the power-of-2 bank stride
   T* s_f1 = reinterpret_cast<T*>(smem);                 // [64][cp]
@@ -87,7 +104,7 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
 
   const float inv_c = 1.0f / c;
   const T* my_f1 = s_f1 + lane * cp;
-  float* out_b = out + ((long long)bi * NDISP) * hw + (long long)y * w + x;
+  const long long pix = (long long)y * w + x;
 #pragma unroll 3
   for (int d = 0; d < NDISP; ++d) {
     const int dy = d / 9, dx = d % 9;            // 0..8 == offset -4..+4
@@ -95,7 +112,7 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
     float acc = 0.f;
     for (int ci = 0; ci < c; ++ci)
       acc += to_f32<T>(my_f1[ci]) * to_f32<T>(other[ci]);
-    out_b[(long long)d * hw] = acc * inv_c;
+    corr_store(out, bi, pix, d, hw, ldo, leaky, acc * inv_c);
   }
 }
 
@@ -103,8 +120,8 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
 template <typename T>
 __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
                                  const T* __restrict__ f2p,   // padded NHWC
-                                 float* __restrict__ out, int b, int c,
-                                 int h, int w) {
+                                 void* __restrict__ out, int b, int c,
+                                 int h, int w, int ldo, int leaky) {
   const int wp = w + 2 * MAXD;
   const long long hw = (long long)h * w;
   const int lane = threadIdx.x & 63;
@@ -128,7 +145,6 @@ __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
     reg1[k] = (k < nchunk && ci < c) ? to_f32<T>(src1[ci]) : 0.f;
   }
   const float inv_c = 1.0f / c;
-  float* out_b = out + ((long long)bi * NDISP) * hw + pix;
   for (int d = 0; d < NDISP; ++d) {
     const int dy = d / 9, dx = d % 9;
     const T* src2 =
@@ -140,25 +156,27 @@ __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
       if (k < nchunk && ci < c) acc += reg1[k] * to_f32<T>(src2[ci]);
     }
     acc = wave_reduce_sum(acc);
-    if (lane == 0) out_b[(long long)d * hw] = acc * inv_c;
+    if (lane == 0) corr_store(out, bi, pix, d, hw, ldo, leaky, acc * inv_c);
   }
 }
 
 template <typename T>
 void launch_corr(const void* f1, const void* f1p, const void* f2p, void* out,
-                 int b, int c, int h, int w, hipStream_t stream) {
+                 int b, int c, int h, int w, int ldo, int leaky,
+                 hipStream_t stream) {
   if (c <= 64) {
     dim3 grid((w + 7) / 8, (h + 7) / 8, b);
     size_t lds = (size_t)(64 + 256) * (c + 1) * sizeof(T);
     hipLaunchKernelGGL((corr_tiled_kernel<T>), grid, dim3(64), lds, stream,
-                       (const T*)f1, (const T*)f2p, (float*)out, b, c, h, w);
+                       (const T*)f1, (const T*)f2p, out, b, c, h, w, ldo,
+                       leaky);
   } else {
     const int waves_per_block = 4;
     long long npix = (long long)b * h * w;
     long long nblocks = (npix + waves_per_block - 1) / waves_per_block;
     hipLaunchKernelGGL((corr_wave_kernel<T>), dim3((unsigned)nblocks),
                        dim3(waves_per_block * 64), 0, stream, (const T*)f1p,
-                       (const T*)f2p, (float*)out, b, c, h, w);
+                       (const T*)f2p, out, b, c, h, w, ldo, leaky);
   }
 }
 
@@ -190,16 +208,22 @@ void vfa_corr_repack(const void* in, void* out, int b, int c, int h, int w,
 }
 
 // f1: NCHW original; f1p/f2p: padded NHWC (from vfa_corr_repack);
-// out: (B, 81, H, W) float32
+// out: (B, 81, H, W) float32 when ldo == 0; with ldo > 0 the first of the
+// 81 bf16 slice channels of pixel 0 in an NHWC buffer of pixel stride ldo
 void vfa_pwc_correlation(const void* f1, const void* f1p, const void* f2p,
                          void* out, int b, int c, int h, int w, int dtype,
-                         hipStream_t stream) {
+                         int ldo, int leaky, hipStream_t stream) {
   switch (dtype) {
-    case VFA_F32: launch_corr<float>(f1, f1p, f2p, out, b, c, h, w, stream); break;
+    case VFA_F32:
+      launch_corr<float>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky, stream);
+      break;
     case VFA_BF16:
-      launch_corr<__hip_bfloat16>(f1, f1p, f2p, out, b, c, h, w, stream); break;
+      launch_corr<__hip_bfloat16>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky,
+                                  stream);
+      break;
     case VFA_F16:
-      launch_corr<__half>(f1, f1p, f2p, out, b, c, h, w, stream); break;
+      launch_corr<__half>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky, stream);
+      break;
   }
 }
 
