@@ -1,10 +1,11 @@
-"""Debug: spy every F.conv2d/conv3d/linear during forwards of all families."""
+"""Debug: spy every F.conv2d/conv3d/conv_transpose2d during forwards of all
+families."""
 import os, sys; sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import torch, torch.nn.functional as F
 from video_features_amd.utils.fold_bn import fold_batchnorms
 
 leaks = []
-for name in ('conv2d', 'conv3d'):
+for name in ('conv2d', 'conv3d', 'conv_transpose2d'):
     orig = getattr(F, name)
     def spy(x, w, *a, _n=name, _o=orig, **k):
         leaks.append((_n, tuple(x.shape), tuple(w.shape)))
@@ -19,7 +20,8 @@ def run(tag, fn):
     with torch.no_grad():
         fn()
     torch.cuda.synchronize()
-    print(tag, 'leaks:', len(leaks))
+    print(tag, 'leaks:', len(leaks), '| conv_transpose2d call sites:',
+          sum(l[0] == 'conv_transpose2d' for l in leaks))
     for l in leaks[:40]:
         print('  ', l)
 

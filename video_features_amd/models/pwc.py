@@ -27,6 +27,16 @@ dilated refiner convs run on the same implicit-GEMM kernel: no cat, no
 NCHW conv.  The path is plain ``ops.conv2d_mod`` / ``ops.pwc_correlation``
 calls, so on CPU it is a pure-torch re-expression of the cat path.
 ``VFA_NO_PWC_CL=1`` forces the cat path.
+
+On the GPU in bf16 the dense-buffer path is channels_last end to end
+(``PWCNet._nhwc``): a level's buffer is allocated BEFORE the previous
+level's upsamplers run, ``upflow`` / ``upfeat`` write their two channels
+each straight into it through ``ops.conv_transpose2d_mod`` (``upfeat``
+reading the previous buffer in place), the warp reads the channels_last
+``f2`` and the ``upflow`` slice view with the warp scale folded in, and the
+cost volume reads the channels_last ``f1`` and warped ``f2``: no NCHW
+feature tensor and no library convolution.  ``VFA_NO_PWC_NHWC=1`` restores
+the earlier dense path (NCHW warp / correlation inputs, eager upsamplers).
 """
 from __future__ import annotations
 
@@ -74,8 +84,7 @@ class PyramidExtractor(nn.Module):
     def forward(self, x: torch.Tensor) -> List[torch.Tensor]:
         if x.is_cuda and x.dtype == torch.bfloat16:
             # channels_last through the pyramid so the fused conv kernel
-            # runs; the decoder's correlation kernel wants NCHW, its
-            # .contiguous() converts per level
+            # runs; warp and correlation read it as it is
             x = x.contiguous(memory_format=torch.channels_last)
         feats = []
         for level in self.levels:
@@ -114,12 +123,15 @@ class Decoder(nn.Module):
                 upflow: Optional[torch.Tensor],
                 upfeat: Optional[torch.Tensor],
                 warp_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        # NCHW copies of the (on the GPU channels_last) pyramid features:
+        # this path keeps the NCHW warp and cost-volume kernels
+        f1n, f2n = f1.contiguous(), f2.contiguous()
         if self.top:
-            corr = F.leaky_relu(ops.pwc_correlation(f1, f2), 0.1)
+            corr = F.leaky_relu(ops.pwc_correlation(f1n, f2n), 0.1)
             x = corr
         else:
-            warped = ops.bilinear_warp(f2, upflow * warp_scale)
-            corr = F.leaky_relu(ops.pwc_correlation(f1, warped), 0.1)
+            warped = ops.bilinear_warp(f2n, upflow * warp_scale)
+            corr = F.leaky_relu(ops.pwc_correlation(f1n, warped), 0.1)
             x = torch.cat([corr, f1, upflow, upfeat], dim=1)
         for conv in self.convs:
             x = torch.cat([conv(x), x], dim=1)
@@ -137,20 +149,54 @@ class Decoder(nn.Module):
                       warp_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
         """Same result as ``forward``; the second return value is the
         level's buffer, of which channels [0, out_channels) are ``x``."""
-        b, fc, h, w = f1.shape
-        width = (self.out_channels + 7) // 8 * 8
-        # allocated per forward (a captured graph replays the allocation)
-        buf = torch.zeros((b, h, w, width), dtype=f1.dtype,
-                          device=f1.device).permute(0, 3, 1, 2)
+        fc = f1.shape[1]
+        buf = self.new_buffer(f1)
+        # the NCHW warp and cost-volume kernels, as in ``forward``
+        f1n, f2n = f1.contiguous(), f2.contiguous()
         if not self.top:
-            f2 = ops.bilinear_warp(f2, upflow * warp_scale)
-        ops.pwc_correlation(f1, f2, out=buf, out_off=self.CORR_OFF,
+            f2n = ops.bilinear_warp(f2n, upflow * warp_scale)
+        ops.pwc_correlation(f1n, f2n, out=buf, out_off=self.CORR_OFF,
                             act='leaky_relu')
         if not self.top:
             o = self.CORR_OFF + 81
             buf[:, o:o + fc] = f1
             buf[:, o + fc:o + fc + 2] = upflow
             buf[:, o + fc + 2:o + fc + 4] = upfeat
+        return self._dense_convs(buf)
+
+    def new_buffer(self, f1: torch.Tensor) -> torch.Tensor:
+        """The level's zero-initialised channels_last buffer; allocated per
+        forward (a captured graph replays the allocation)."""
+        b, _, h, w = f1.shape
+        width = (self.out_channels + 7) // 8 * 8
+        return torch.zeros((b, h, w, width), dtype=f1.dtype,
+                           device=f1.device).permute(0, 3, 1, 2)
+
+    def up_off(self, fc: int) -> int:
+        """First channel of ``upflow`` in the buffer (``upfeat`` follows)."""
+        return self.CORR_OFF + 81 + fc
+
+    def forward_nhwc(self, f1: torch.Tensor, f2: torch.Tensor,
+                     buf: torch.Tensor, warp_scale: float
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``forward_dense`` on channels_last features.  ``buf`` is
+        ``new_buffer(f1)``; below the top level the caller has already let
+        the previous level's upsamplers write its ``upflow`` / ``upfeat``
+        channels."""
+        fc = f1.shape[1]
+        if not self.top:
+            o = self.up_off(fc)
+            f2 = ops.bilinear_warp(f2, buf[:, o:o + 2], scale=warp_scale)
+        ops.pwc_correlation(f1, f2, out=buf, out_off=self.CORR_OFF,
+                            act='leaky_relu')
+        if not self.top:
+            o = self.CORR_OFF + 81
+            buf[:, o:o + fc] = f1
+        return self._dense_convs(buf)
+
+    def _dense_convs(self, buf: torch.Tensor
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The five dense convs and the flow head on a filled buffer."""
         for conv, off in zip(self.convs, self.DENSE_OFF):
             ops.conv2d_mod(conv[0], buf, 'leaky_relu', out=buf, out_off=off,
                            in_off=off + conv[0].out_channels)
@@ -199,6 +245,14 @@ class PWCNet(nn.Module):
         self.decoder2 = Decoder(ch[1], last=True)
         self.refiner = Refiner(self.decoder2.out_channels)
 
+    def _nhwc(self, x: torch.Tensor) -> bool:
+        """Channels_last end to end: the dense-buffer path on the GPU in
+        bf16 with the extension loaded, unless VFA_NO_PWC_NHWC=1."""
+        return (self._dense(x) and x.is_cuda and x.dtype == torch.bfloat16
+                and ops.hip_available()
+                and not ops._env_flag('VFA_FORCE_TORCH_OPS')
+                and not ops._env_flag('VFA_NO_PWC_NHWC'))
+
     def _dense(self, x: torch.Tensor) -> bool:
         if ops._env_flag('VFA_NO_PWC_CL'):
             return False
@@ -231,10 +285,26 @@ class PWCNet(nn.Module):
         def run(dec, *args):
             return dec.forward_dense(*args) if dense else dec(*args)
 
+        nhwc = self._nhwc(p1[0])
         # pyramid list index: level l features are p[l-1] (1/2^l resolution)
-        flow, feat = run(self.decoder6, p1[5], p2[5], None, None, 0.0)
+        if nhwc:
+            flow, feat = self.decoder6.forward_nhwc(
+                p1[5], p2[5], self.decoder6.new_buffer(p1[5]), 0.0)
+        else:
+            flow, feat = run(self.decoder6, p1[5], p2[5], None, None, 0.0)
         for lvl in (5, 4, 3, 2):
             prev_dec = decs[lvl + 1]
+            if nhwc:
+                dec, f1 = decs[lvl], p1[lvl - 1]
+                buf = dec.new_buffer(f1)
+                o = dec.up_off(f1.shape[1])
+                ops.conv_transpose2d_mod(prev_dec.upflow, flow, out=buf,
+                                         out_off=o)
+                ops.conv_transpose2d_mod(prev_dec.upfeat, feat, out=buf,
+                                         out_off=o + 2, in_off=0)
+                flow, feat = dec.forward_nhwc(f1, p2[lvl - 1], buf,
+                                              self.WARP_SCALES[lvl])
+                continue
             upflow = prev_dec.upflow(flow)
             upfeat = prev_dec.upfeat(
                 feat[:, :prev_dec.out_channels] if dense else feat)

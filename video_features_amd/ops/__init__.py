@@ -192,6 +192,11 @@ def pwc_correlation(f1: torch.Tensor, f2: torch.Tensor,
     its channels [out_off, out_off + 81) and ``out`` is returned; on GPU
     ``out`` is a channels_last bf16 buffer and the kernels store the slice
     themselves (no f32 NCHW tensor, cast or copy).
+
+    bf16 ``f1`` and ``f2`` that are channels_last-contiguous (and not also
+    NCHW-contiguous) are read in place by the NHWC kernel variants: no
+    repack, no padded copy, any C <= 256; a result without ``out`` is then
+    channels_last as well.  NCHW inputs keep the repack kernels.
     """
     if act not in ('none', 'leaky_relu'):
         raise ValueError(f'pwc_correlation: unsupported act {act!r}')
@@ -200,6 +205,15 @@ def pwc_correlation(f1: torch.Tensor, f2: torch.Tensor,
         direct = out is None or (
             out.dtype == torch.bfloat16
             and out.is_contiguous(memory_format=torch.channels_last))
+        if (max_disp == 4 and f1.dtype == torch.bfloat16
+                and f2.dtype == torch.bfloat16 and _cl_only(f1)
+                and _cl_only(f2)):
+            y = _ext.pwc_correlation_nhwc(f1, f2, out if direct else None,
+                                          out_off, leaky)
+            if direct:
+                return y
+            out[:, out_off:out_off + y.shape[1]] = y
+            return out
         y = _ext.pwc_correlation(f1.contiguous(), f2.contiguous(), max_disp,
                                  out if direct else None, out_off, leaky)
         if direct:
@@ -228,12 +242,39 @@ def _pwc_correlation_torch(f1: torch.Tensor, f2: torch.Tensor,
     return out
 
 
-def bilinear_warp(x: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
+def _cl_only(t: torch.Tensor) -> bool:
+    """4-D, channels_last-contiguous and not also NCHW-contiguous (C == 1 or
+    H == W == 1 tensors are both; they count as NCHW)."""
+    return (t.dim() == 4
+            and t.is_contiguous(memory_format=torch.channels_last)
+            and not t.is_contiguous())
+
+
+def bilinear_warp(x: torch.Tensor, flow: torch.Tensor,
+                  scale: float = 1.0) -> torch.Tensor:
     """Backward-warp ``x`` (B, C, H, W) by ``flow`` (B, 2, H, W) with border
     zero-masking semantics matching the reference's PWC ``Backward`` warp
-    (reference models/pwc/pwc_src/pwc_net.py:23-41)."""
+    (reference models/pwc/pwc_src/pwc_net.py:23-41).  The sample point is
+    (x + scale*fx, y + scale*fy); a sample counts only when it lies fully
+    inside the image.
+
+    A bf16 ``x`` that is channels_last-contiguous (and not also
+    NCHW-contiguous) with C % 8 == 0 runs the NHWC kernel: the result is
+    channels_last, the scale is applied in f32 inside the kernel and
+    ``flow`` is read through its strides (a 2-channel slice view of a wider
+    channels_last buffer included), no copy of it is made.  NCHW inputs keep
+    the NCHW kernel; there and on the CPU ``scale`` multiplies the flow."""
     if _use_hip(x):
+        if (x.dtype == torch.bfloat16 and _cl_only(x)
+                and x.shape[1] % 8 == 0):
+            if flow.dtype != torch.bfloat16:
+                flow = flow.to(torch.bfloat16)
+            return _ext.bilinear_warp_nhwc(x, flow, float(scale))
+        if scale != 1.0:
+            flow = flow * scale
         return _ext.bilinear_warp(x.contiguous(), flow.contiguous())
+    if scale != 1.0:
+        flow = flow * scale
     b, c, h, w = x.shape
     yy, xx = torch.meshgrid(
         torch.arange(h, device=x.device, dtype=x.dtype),
@@ -732,6 +773,186 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
     if res is not None:
         y = y + res
     y = _apply_act(y, act)
+    if out is not None:
+        out[:, out_off:out_off + y.shape[1]] = y
+        return out
+    return y
+
+
+# ------------------------------------------------- transposed convolution
+def _pack_tconv_weight(w: torch.Tensor, c8: int) -> torch.Tensor:
+    """(C, K_out, 4, 4) transposed-conv weight -> the (16*K_out, c8) matrix
+    of the P-form GEMM: row (ky*4 + kx)*K_out + ko holds W[:, ko, ky, kx],
+    zero columns for the channels c8 adds."""
+    c, kout, kh, kw = w.shape
+    if (kh, kw) != (4, 4) or c8 < c:
+        raise ValueError(f'_pack_tconv_weight: weight {tuple(w.shape)}, '
+                         f'c8={c8}')
+    wp = w.permute(2, 3, 1, 0).reshape(16 * kout, c)
+    if c8 > c:
+        wp = torch.nn.functional.pad(wp, (0, c8 - c))
+    return wp.contiguous()
+
+
+def _conv_transpose2d_pform(x: torch.Tensor, w: torch.Tensor,
+                            bias: Optional[torch.Tensor] = None
+                            ) -> torch.Tensor:
+    """Pure-torch P-form of the 4x4 / stride 2 / padding 1 transposed conv,
+    with the index arithmetic of the kernels (tconv.hip): the partials
+    P[pixel, (ky, kx, ko)] = x[pixel, :] @ Wp^T, then the col2im gather in
+    which output row oy takes tap ky = (oy + 1) % 2 from input row
+    (oy + 1 - ky) / 2 and tap ky + 2 from the row above it."""
+    b, c, h, wd = x.shape
+    kout = w.shape[1]
+    wp = _pack_tconv_weight(w, c)
+    p = (x.permute(0, 2, 3, 1).reshape(-1, c) @ wp.t()).reshape(
+        b, h, wd, 4, 4, kout)
+    out = x.new_zeros(b, 2 * h, 2 * wd, kout)
+    oy = torch.arange(2 * h)
+    ox = torch.arange(2 * wd)
+    ky0, kx0 = (oy + 1) % 2, (ox + 1) % 2
+    iy0, ix0 = (oy + 1 - ky0) // 2, (ox + 1 - kx0) // 2
+    for ty in (0, 1):
+        iy, ky = iy0 - ty, ky0 + 2 * ty
+        vy = (iy >= 0) & (iy < h)
+        for tx in (0, 1):
+            ix, kx = ix0 - tx, kx0 + 2 * tx
+            vx = (ix >= 0) & (ix < wd)
+            g = p[:, iy.clamp(0, h - 1)[:, None], ix.clamp(0, wd - 1)[None],
+                  ky[:, None], kx[None]]               # (B, 2H, 2W, K_out)
+            out += g * (vy[:, None] & vx[None])[None, :, :, None].to(g.dtype)
+    if bias is not None:
+        out = out + bias
+    return out.permute(0, 3, 1, 2)
+
+
+def _tconv_kernel_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding
+                     ) -> bool:
+    """The geometry, dtype and device tconv.hip covers (layout aside)."""
+    st = (stride, stride) if isinstance(stride, int) else tuple(stride)
+    pd = (padding, padding) if isinstance(padding, int) else tuple(padding)
+    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16 and weight.dim() == 4
+            and tuple(weight.shape[2:]) == (4, 4) and weight.shape[1] <= 2
+            and st == (2, 2) and pd == (1, 1)
+            and not _env_flag('VFA_NO_TCONV') and _use_hip(x))
+
+
+def _tconv_check_out(x: torch.Tensor, out: Optional[torch.Tensor],
+                     name: str) -> None:
+    if out is not None and (out.untyped_storage().data_ptr()
+                            == x.untyped_storage().data_ptr()):
+        raise ValueError(f'{name}: out must not share storage with x')
+
+
+def _tconv_out_direct(out: Optional[torch.Tensor]) -> bool:
+    """Whether the kernels can store into ``out`` themselves."""
+    return out is None or (
+        out.is_cuda and out.dtype == torch.bfloat16 and out.dim() == 4
+        and out.is_contiguous(memory_format=torch.channels_last))
+
+
+# widest input slice whose packed weight (32 rows) fits the 64 KiB of LDS
+_TCONV_MAX_C = 992
+
+
+def conv_transpose2d_act(x: torch.Tensor, weight: torch.Tensor,
+                         bias: Optional[torch.Tensor] = None,
+                         stride=2, padding=1,
+                         out: Optional[torch.Tensor] = None,
+                         out_off: int = 0, in_off: int = 0,
+                         in_ch: Optional[int] = None) -> torch.Tensor:
+    """Transposed convolution, ``weight`` (C_in, K_out, KH, KW).
+
+    GPU kernel path (tconv.hip): kernel 4x4, stride 2, padding 1 (no
+    output_padding, dilation 1, groups 1), K_out <= 2, bf16 in and out with
+    f32 accumulation and one rounding.  Channels_last ``x`` with
+    C % 8 == 0 runs the P-form (an MFMA GEMM to f32 partials, then a col2im
+    gather); any unsliced ``x`` with C <= 16, NCHW or channels_last, runs
+    the direct kernel.  Everything else -- the CPU, other dtypes, other
+    geometry, other layouts -- is the ``F.conv_transpose2d`` composition:
+    slice, call, assign into ``out[:, out_off:...]``.
+
+    ``in_ch`` makes ``x`` a wider buffer of which channels
+    [in_off, in_off + in_ch) are read, in place on the kernel path (in_off,
+    in_ch and the buffer width multiples of 8).  ``out`` / ``out_off`` write
+    channels [out_off, out_off + K_out) of a wider buffer and nothing else
+    (out_off may be odd); ``out`` must not share storage with ``x``
+    (ValueError).  Without ``out`` the kernel path returns a new
+    channels_last (B, K_out, 2H, 2W) tensor.  ``VFA_NO_TCONV=1`` forces
+    the composition."""
+    if in_ch is None:
+        if in_off:
+            raise ValueError('conv_transpose2d_act: in_off needs in_ch')
+        cx = x.shape[1]
+    else:
+        cx = in_ch
+    _tconv_check_out(x, out, 'conv_transpose2d_act')
+    if (weight.shape[0] == cx and _tconv_out_direct(out)
+            and _tconv_kernel_ok(x, weight, stride, padding)):
+        if in_ch is None and cx <= 16:
+            return _ext.conv_transpose2d_small(x, weight.contiguous(), bias,
+                                               out, out_off)
+        if (x.is_contiguous(memory_format=torch.channels_last)
+                and cx % 8 == 0 and in_off % 8 == 0 and x.shape[1] % 8 == 0
+                and cx <= _TCONV_MAX_C):
+            return _ext.conv_transpose2d_nhwc(
+                x, _pack_tconv_weight(weight, cx), bias, out, out_off,
+                in_off, 0 if in_ch is None else in_ch)
+    if in_ch is not None:
+        x = x[:, in_off:in_off + in_ch]
+    y = torch.nn.functional.conv_transpose2d(x, weight, bias, stride, padding)
+    if out is not None:
+        out[:, out_off:out_off + y.shape[1]] = y
+        return out
+    return y
+
+
+def conv_transpose2d_mod(m: torch.nn.Module, x: torch.Tensor,
+                         out: Optional[torch.Tensor] = None,
+                         out_off: int = 0,
+                         in_off: Optional[int] = None) -> torch.Tensor:
+    """Route an ``nn.ConvTranspose2d`` call through tconv.hip (see
+    ``conv_transpose2d_act`` for the geometry the kernels cover); the
+    module's own forward otherwise.
+
+    ``in_off``: ``x`` is a wide buffer and the conv reads ``m.in_channels``
+    channels starting at ``in_off``.  On the kernel path the slice width is
+    ``m.in_channels`` rounded up to a multiple of 8 and the packed weight
+    (cached on the module, keyed on the weight's version, dtype, device and
+    pointer) has zero rows for the channels the rounding adds -- the
+    contract of ``conv2d_mod``: those channels must exist in the buffer and
+    be finite."""
+    w = m.weight
+    sliced = in_off is not None
+    c = m.in_channels if sliced else x.shape[1]
+    c8 = (c + 7) // 8 * 8
+    _tconv_check_out(x, out, 'conv_transpose2d_mod')
+    eligible = (m.groups == 1 and tuple(m.dilation) == (1, 1)
+                and tuple(m.output_padding) == (0, 0)
+                and c == m.in_channels and _tconv_out_direct(out)
+                and _tconv_kernel_ok(x, w, m.stride, m.padding))
+    if eligible and not sliced and c <= 16:
+        return _ext.conv_transpose2d_small(x, w.contiguous(), m.bias, out,
+                                           out_off)
+    if (eligible and c8 <= _TCONV_MAX_C
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and (sliced or c8 == c)):
+        if sliced and (in_off % 8 or x.shape[1] % 8
+                       or in_off + c8 > x.shape[1]):
+            raise ValueError(
+                f'conv_transpose2d_mod: slice [{in_off}, {in_off + c8}) of '
+                f'a {x.shape[1]}-channel buffer needs in_off and the buffer '
+                'width to be multiples of 8 and the rounded slice inside it')
+        key = (w._version, w.dtype, w.device, w.data_ptr(), c8)
+        ent = getattr(m, '_vfa_tconv_wp', None)
+        if ent is None or ent[0] != key:
+            with torch.no_grad():
+                m._vfa_tconv_wp = ent = (key, _pack_tconv_weight(w, c8))
+        return _ext.conv_transpose2d_nhwc(x, ent[1], m.bias, out, out_off,
+                                          in_off if sliced else 0,
+                                          c8 if sliced else 0)
+    y = m(x[:, in_off:in_off + c] if sliced else x)
     if out is not None:
         out[:, out_off:out_off + y.shape[1]] = y
         return out

@@ -15,6 +15,17 @@ void vfa_layer_norm(const void*, const void*, const void*, void*, long long,
                     int, float, int, hipStream_t);
 void vfa_bilinear_warp(const void*, const void*, void*, int, int, int, int,
                        int, hipStream_t);
+void vfa_bilinear_warp_nhwc(const void*, const void*, void*, int, int, int,
+                            int, long long, long long, long long, long long,
+                            float, hipStream_t);
+void vfa_pwc_correlation_nhwc(const void*, const void*, void*, int, int, int,
+                              int, int, int, hipStream_t);
+long long vfa_tconv_lds_bytes(int, int);
+void vfa_tconv_pform(const void*, const void*, const void*, void*, void*, int,
+                     int, int, int, int, int, int, hipStream_t);
+void vfa_tconv_direct(const void*, const void*, const void*, void*, int, int,
+                      int, int, long long, long long, long long, long long,
+                      int, int, hipStream_t);
 void vfa_grid_sample(const void*, const void*, void*, long long, int, int,
                      int, int, int, int, hipStream_t);
 void vfa_corr_repack(const void*, void*, int, int, int, int, int,
@@ -147,6 +158,71 @@ torch::Tensor bilinear_warp(torch::Tensor x, torch::Tensor flow) {
   vfa_bilinear_warp(x.data_ptr(), flow_c.data_ptr(), out.data_ptr(),
                     (int)x.size(0), (int)x.size(1), (int)x.size(2),
                     (int)x.size(3), dtype_tag(x), current_stream());
+  return out;
+}
+
+bool cl_only(const torch::Tensor& t) {
+  return t.dim() == 4 &&
+         t.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
+         !t.is_contiguous();
+}
+
+// x channels_last bf16 (C % 8 == 0); flow bf16 (B, 2, H, W) of ANY strides,
+// read in place; sample point (x + scale*fx, y + scale*fy); channels_last
+// result
+torch::Tensor bilinear_warp_nhwc(torch::Tensor x, torch::Tensor flow,
+                                 double scale) {
+  TORCH_CHECK(x.is_cuda() && cl_only(x) &&
+                  x.scalar_type() == torch::kBFloat16 && x.size(1) % 8 == 0,
+              "bilinear_warp_nhwc: x must be channels_last bf16, C % 8 == 0");
+  TORCH_CHECK(flow.is_cuda() && flow.dim() == 4 && flow.size(1) == 2 &&
+                  flow.scalar_type() == torch::kBFloat16 &&
+                  flow.size(0) == x.size(0) && flow.size(2) == x.size(2) &&
+                  flow.size(3) == x.size(3),
+              "bilinear_warp_nhwc: flow must be bf16 (B, 2, H, W)");
+  auto out = torch::empty_like(x);   // preserves channels_last
+  TORCH_CHECK(cl_only(out) || out.numel() == 0);
+  if (x.numel() == 0) return out;
+  vfa_bilinear_warp_nhwc(x.data_ptr(), flow.data_ptr(), out.data_ptr(),
+                         (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                         (int)x.size(3), flow.stride(0), flow.stride(1),
+                         flow.stride(2), flow.stride(3), (float)scale,
+                         current_stream());
+  return out;
+}
+
+// f1, f2 channels_last bf16, read unpadded and in place.  out_buf as in
+// pwc_correlation; without it the result is a channels_last bf16
+// (B, 81, H, W) tensor
+torch::Tensor pwc_correlation_nhwc(torch::Tensor f1, torch::Tensor f2,
+                                   c10::optional<torch::Tensor> out_buf,
+                                   int64_t out_off, bool leaky) {
+  TORCH_CHECK(f1.is_cuda() && f2.is_cuda() && cl_only(f1) && cl_only(f2) &&
+                  f1.scalar_type() == torch::kBFloat16 &&
+                  f2.scalar_type() == torch::kBFloat16,
+              "pwc_correlation_nhwc: inputs must be channels_last bf16");
+  TORCH_CHECK(f1.sizes() == f2.sizes());
+  TORCH_CHECK(f1.size(1) <= 256,
+              "corr_wave registers cover C<=256 (PWC max is 196)");
+  const int b = (int)f1.size(0), c = (int)f1.size(1);
+  const int h = (int)f1.size(2), w = (int)f1.size(3);
+  torch::Tensor out;
+  if (out_buf.has_value()) {
+    out = *out_buf;
+    TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
+                out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
+                out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
+                out.size(2) == h && out.size(3) == w && out_off >= 0 &&
+                out_off + 81 <= out.size(1),
+                "out buffer must be CL bf16 (B, >=off+81, H, W)");
+  } else {
+    out_off = 0;
+    out = torch::empty({b, h, w, 81}, f1.options()).permute({0, 3, 1, 2});
+  }
+  vfa_pwc_correlation_nhwc(f1.data_ptr(), f2.data_ptr(),
+                           static_cast<char*>(out.data_ptr()) + out_off * 2,
+                           b, c, h, w, (int)out.size(1), leaky ? 1 : 0,
+                           current_stream());
   return out;
 }
 
@@ -609,6 +685,114 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// Output side of the transposed convs: a new channels_last (B, K, 2H, 2W)
+// tensor, or the channel slice [out_off, out_off + K) of out_buf, which
+// must not overlap x in memory.  Returns (tensor, first slice element, ldo).
+std::tuple<torch::Tensor, void*, int> tconv_out(
+    const torch::Tensor& x, c10::optional<torch::Tensor> out_buf,
+    int64_t out_off, int kout) {
+  const long b = x.size(0), oh = 2 * x.size(2), ow = 2 * x.size(3);
+  if (!out_buf.has_value()) {
+    TORCH_CHECK(out_off == 0, "out_off needs out");
+    auto out = torch::empty({b, oh, ow, (long)kout}, x.options())
+                   .permute({0, 3, 1, 2});
+    return {out, out.data_ptr(), kout};
+  }
+  auto out = *out_buf;
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
+              out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
+              out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
+              out.size(2) == oh && out.size(3) == ow && out_off >= 0 &&
+              out_off + kout <= out.size(1),
+              "out buffer must be CL bf16 (B, >=off+K_out, 2H, 2W)");
+  if (x.numel() > 0 && out.numel() > 0) {
+    // extent of x through its strides (it may be any strided view)
+    long long span = 1;
+    for (int d = 0; d < 4; ++d) span += (x.size(d) - 1) * x.stride(d);
+    const char* xb = static_cast<const char*>(x.data_ptr());
+    const char* ob = static_cast<const char*>(out.data_ptr());
+    TORCH_CHECK(!(xb < ob + out.numel() * 2 && ob < xb + span * 2),
+                "conv_transpose2d: out must not overlap x in memory");
+  }
+  return {out, static_cast<char*>(out.data_ptr()) + out_off * 2,
+          (int)out.size(1)};
+}
+
+// P-form transposed conv (4x4, stride 2, padding 1).  x channels_last bf16;
+// wp the packed (16*K_out, C) weight; in_ch > 0: x is a wider buffer and
+// channels [in_off, in_off + in_ch) are read in place.
+torch::Tensor conv_transpose2d_nhwc(torch::Tensor x, torch::Tensor wp,
+                                    c10::optional<torch::Tensor> bias,
+                                    c10::optional<torch::Tensor> out_buf,
+                                    int64_t out_off, int64_t in_off,
+                                    int64_t in_ch) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && cl_contig(x) &&
+                  x.scalar_type() == torch::kBFloat16,
+              "x must be channels_last bf16");
+  const int xc = (int)x.size(1);
+  const bool slice = in_ch > 0;
+  if (!slice) TORCH_CHECK(in_off == 0 && in_ch == 0, "in_off needs in_ch > 0");
+  const int c = slice ? (int)in_ch : xc;
+  TORCH_CHECK(in_off >= 0 && in_off % 8 == 0 && c % 8 == 0 && xc % 8 == 0 &&
+                  in_off + c <= xc,
+              "conv_transpose2d_nhwc: in_off, in_ch and the buffer width "
+              "must be multiples of 8 and the slice inside the buffer");
+  TORCH_CHECK(wp.is_cuda() && wp.dim() == 2 && wp.is_contiguous() &&
+                  wp.scalar_type() == torch::kBFloat16 && wp.size(1) == c &&
+                  (wp.size(0) == 16 || wp.size(0) == 32),
+              "packed weight must be bf16 (16*K_out, C), K_out <= 2");
+  const int kout = (int)wp.size(0) / 16;
+  TORCH_CHECK(vfa_tconv_lds_bytes(c, kout) <= 64 * 1024,
+              "conv_transpose2d_nhwc: C too large for the LDS-resident weight");
+  const int b = (int)x.size(0), h = (int)x.size(2), w = (int)x.size(3);
+  const void* bptr = nullptr;
+  torch::Tensor bc;
+  if (bias.has_value()) {
+    bc = bias->contiguous().to(torch::kBFloat16);
+    TORCH_CHECK(bc.numel() == kout);
+    bptr = bc.data_ptr();
+  }
+  auto [out, optr, ldo] = tconv_out(x, out_buf, out_off, kout);
+  if (x.numel() == 0) return out;
+  auto part = torch::empty({(long)b * h * w, 16L * kout},
+                           x.options().dtype(torch::kFloat32));
+  vfa_tconv_pform(static_cast<const char*>(x.data_ptr()) + in_off * 2,
+                  wp.data_ptr(), bptr, part.data_ptr(), optr, b, h, w, c, xc,
+                  kout, ldo, current_stream());
+  return out;
+}
+
+// direct transposed conv for C <= 16: x bf16 of any strides, w (C, K_out,
+// 4, 4) contiguous bf16
+torch::Tensor conv_transpose2d_small(torch::Tensor x, torch::Tensor w,
+                                     c10::optional<torch::Tensor> bias,
+                                     c10::optional<torch::Tensor> out_buf,
+                                     int64_t out_off) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == torch::kBFloat16 && x.size(1) <= 16,
+              "x must be bf16 (B, C <= 16, H, W)");
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.is_contiguous() &&
+                  w.scalar_type() == torch::kBFloat16 &&
+                  w.size(0) == x.size(1) && w.size(1) >= 1 &&
+                  w.size(1) <= 2 && w.size(2) == 4 && w.size(3) == 4,
+              "weight must be contiguous bf16 (C, K_out <= 2, 4, 4)");
+  const int kout = (int)w.size(1);
+  const void* bptr = nullptr;
+  torch::Tensor bc;
+  if (bias.has_value()) {
+    bc = bias->contiguous().to(torch::kBFloat16);
+    TORCH_CHECK(bc.numel() == kout);
+    bptr = bc.data_ptr();
+  }
+  auto [out, optr, ldo] = tconv_out(x, out_buf, out_off, kout);
+  if (x.numel() == 0) return out;
+  vfa_tconv_direct(x.data_ptr(), w.data_ptr(), bptr, optr, (int)x.size(0),
+                   (int)x.size(1), (int)x.size(2), (int)x.size(3),
+                   x.stride(0), x.stride(1), x.stride(2), x.stride(3), kout,
+                   ldo, current_stream());
+  return out;
+}
+
 // (BM, BN) of the tile conv2d_nhwc runs for M = B*OH*OW and kout — the
 // same host function launch_conv calls, so tests can pin a case to a tile
 std::tuple<int64_t, int64_t> conv2d_tile(int64_t m, int64_t kout) {
@@ -713,6 +897,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_act", &linear_act);
   m.def("conv2d_nhwc", &conv2d_nhwc);
   m.def("conv2d_tile", &conv2d_tile);
+  m.def("conv_transpose2d_nhwc", &conv_transpose2d_nhwc);
+  m.def("conv_transpose2d_small", &conv_transpose2d_small);
+  m.def("bilinear_warp_nhwc", &bilinear_warp_nhwc);
+  m.def("pwc_correlation_nhwc", &pwc_correlation_nhwc);
   m.def("temporal_merge", &temporal_merge);
   m.def("avgpool2d_nhwc", &avgpool2d_nhwc);
   m.def("attnpool_tokens", &attnpool_tokens);

@@ -21,6 +21,11 @@
 // pixel stride is ldo elements (the host folds out_off into the pointer):
 // the PWC decoder's dense buffer, no NCHW tensor, cast or cat in between.
 // leaky != 0 applies LeakyReLU(0.1) before the store in either mode.
+//
+// channels_last inputs (vfa_pwc_correlation_nhwc): the NHWC = true variants
+// of both kernels read the unpadded tensors directly, out-of-image taps
+// contribute zero through a bounds check at staging (tiled) or a
+// wave-uniform check per displacement (wave): no repack, no padded copy.
 #include "vfa_common.h"
 
 namespace {
@@ -65,9 +70,12 @@ __global__ void repack_kernel(const T* __restrict__ in, T* __restrict__ out,
 }
 
 // ------------------------------------------------------------ corr_tiled
-template <typename T>
-__global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
-                                  const T* __restrict__ f2p,  // padded NHWC
+// NHWC = false: f1 NCHW, f2p the zero-padded NHWC repack.
+// NHWC = true: f1 and f2p are the UNPADDED channels_last tensors; the f2
+// staging bounds-checks and zero-fills the out-of-image taps.
+template <typename T, bool NHWC>
+__global__ void corr_tiled_kernel(const T* __restrict__ f1,
+                                  const T* __restrict__ f2p,
                                   void* __restrict__ out, int b, int c,
                                   int h, int w, int ldo, int leaky) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -85,8 +93,14 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
   // stage f1: each lane loads its own pixel's channel vector (NCHW reads,
   // stride hw — hits L2; done once per 81 reuses)
   if (x < w && y < h) {
-    const T* src = f1 + (long long)bi * c * hw + (long long)y * w + x;
-    for (int ci = 0; ci < c; ++ci) s_f1[lane * cp + ci] = src[(long long)ci * hw];
+    if constexpr (NHWC) {
+      const T* src = f1 + ((long long)bi * hw + (long long)y * w + x) * c;
+      for (int ci = 0; ci < c; ++ci) s_f1[lane * cp + ci] = src[ci];
+    } else {
+      const T* src = f1 + (long long)bi * c * hw + (long long)y * w + x;
+      for (int ci = 0; ci < c; ++ci)
+        s_f1[lane * cp + ci] = src[(long long)ci * hw];
+    }
   }
   // stage f2: 16x16 padded-NHWC patch rooted at (tileY, tileX) in padded
   // coords; 4 pixels per lane, contiguous channel reads
@@ -94,7 +108,15 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
     const int fy = p >> 4, fx = p & 15;
     const int gy = tileY + fy, gx = tileX + fx;   // padded coords
     T* dst = s_f2 + p * cp;
-    if (gy < h + 2 * MAXD && gx < wp) {
+    if constexpr (NHWC) {
+      const int iy = gy - MAXD, ix = gx - MAXD;   // image coords
+      if (iy >= 0 && iy < h && ix >= 0 && ix < w) {
+        const T* src = f2p + ((long long)bi * hw + (long long)iy * w + ix) * c;
+        for (int ci = 0; ci < c; ++ci) dst[ci] = src[ci];
+      } else {
+        for (int ci = 0; ci < c; ++ci) dst[ci] = from_f32<T>(0.f);
+      }
+    } else if (gy < h + 2 * MAXD && gx < wp) {
       const T* src = f2p + (((long long)bi * (h + 2 * MAXD) + gy) * wp + gx) * c;
       for (int ci = 0; ci < c; ++ci) dst[ci] = src[ci];
     }
@@ -117,9 +139,12 @@ __global__ void corr_tiled_kernel(const T* __restrict__ f1,   // NCHW
 }
 
 // ------------------------------------------------------------- corr_wave
-template <typename T>
-__global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
-                                 const T* __restrict__ f2p,   // padded NHWC
+// NHWC = false: both inputs are the zero-padded NHWC repacks.
+// NHWC = true: both are the UNPADDED channels_last tensors; a displacement
+// that leaves the image is a wave-uniform test and stores zero.
+template <typename T, bool NHWC>
+__global__ void corr_wave_kernel(const T* __restrict__ f1p,
+                                 const T* __restrict__ f2p,
                                  void* __restrict__ out, int b, int c,
                                  int h, int w, int ldo, int leaky) {
   const int wp = w + 2 * MAXD;
@@ -137,7 +162,9 @@ __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
   // f1 channel chunk in registers (lane-strided)
   float reg1[4];
   const T* src1 =
-      f1p + (((long long)bi * (h + 2 * MAXD) + y + MAXD) * wp + x + MAXD) * c;
+      NHWC ? f1p + ((long long)bi * hw + pix) * c
+           : f1p + (((long long)bi * (h + 2 * MAXD) + y + MAXD) * wp + x +
+                    MAXD) * c;
   const int nchunk = (c + 63) / 64;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -147,8 +174,18 @@ __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
   const float inv_c = 1.0f / c;
   for (int d = 0; d < NDISP; ++d) {
     const int dy = d / 9, dx = d % 9;
-    const T* src2 =
-        f2p + (((long long)bi * (h + 2 * MAXD) + y + dy) * wp + x + dx) * c;
+    const T* src2;
+    if constexpr (NHWC) {
+      const int y2 = y + dy - MAXD, x2 = x + dx - MAXD;
+      if (y2 < 0 || y2 >= h || x2 < 0 || x2 >= w) {
+        if (lane == 0) corr_store(out, bi, pix, d, hw, ldo, leaky, 0.f);
+        continue;
+      }
+      src2 = f2p + ((long long)bi * hw + (long long)y2 * w + x2) * c;
+    } else {
+      src2 =
+          f2p + (((long long)bi * (h + 2 * MAXD) + y + dy) * wp + x + dx) * c;
+    }
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -160,21 +197,21 @@ __global__ void corr_wave_kernel(const T* __restrict__ f1p,   // padded NHWC
   }
 }
 
-template <typename T>
+template <typename T, bool NHWC = false>
 void launch_corr(const void* f1, const void* f1p, const void* f2p, void* out,
                  int b, int c, int h, int w, int ldo, int leaky,
                  hipStream_t stream) {
   if (c <= 64) {
     dim3 grid((w + 7) / 8, (h + 7) / 8, b);
     size_t lds = (size_t)(64 + 256) * (c + 1) * sizeof(T);
-    hipLaunchKernelGGL((corr_tiled_kernel<T>), grid, dim3(64), lds, stream,
+    hipLaunchKernelGGL((corr_tiled_kernel<T, NHWC>), grid, dim3(64), lds, stream,
                        (const T*)f1, (const T*)f2p, out, b, c, h, w, ldo,
                        leaky);
   } else {
     const int waves_per_block = 4;
     long long npix = (long long)b * h * w;
     long long nblocks = (npix + waves_per_block - 1) / waves_per_block;
-    hipLaunchKernelGGL((corr_wave_kernel<T>), dim3((unsigned)nblocks),
+    hipLaunchKernelGGL((corr_wave_kernel<T, NHWC>), dim3((unsigned)nblocks),
                        dim3(waves_per_block * 64), 0, stream, (const T*)f1p,
                        (const T*)f2p, out, b, c, h, w, ldo, leaky);
   }
@@ -225,6 +262,16 @@ void vfa_pwc_correlation(const void* f1, const void* f1p, const void* f2p,
       launch_corr<__half>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky, stream);
       break;
   }
+}
+
+// f1, f2: unpadded channels_last bf16 (B, C, H, W), C <= 256; out: the first
+// of the 81 bf16 slice channels of pixel 0 in an NHWC buffer of pixel
+// stride ldo > 0.  No repack and no padded copy.
+void vfa_pwc_correlation_nhwc(const void* f1, const void* f2, void* out,
+                              int b, int c, int h, int w, int ldo, int leaky,
+                              hipStream_t stream) {
+  launch_corr<__hip_bfloat16, true>(f1, f1, f2, out, b, c, h, w, ldo, leaky,
+                                    stream);
 }
 
 }  // extern "C"

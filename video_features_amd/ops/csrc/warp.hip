@@ -1,6 +1,8 @@
 // Bilinear gather kernels for optical flow on gfx950:
 //  - vfa_bilinear_warp: backward warp x (B,C,H,W) by flow (B,2,H,W) with
-//    border zero-masking (PWC `Backward`, reference pwc_net.py:23-41)
+//    border zero-masking (PWC `Backward`, reference pwc_net.py:23-41);
+//    vfa_bilinear_warp_nhwc is its channels_last bf16 form with the flow
+//    read through strides and a flow scale
 //  - vfa_grid_sample: RAFT pyramid lookup — pixel-unit coords
 //    (N,Ho,Wo,2), zeros padding, align_corners=True semantics
 //    (reference raft_src/utils/utils.py:57-71)
@@ -46,6 +48,53 @@ __global__ void bilinear_warp_kernel(const T* __restrict__ x,
       }
       ob[(long long)ci * hw + pix] = from_f32<T>(v);
     }
+  }
+}
+
+// channels_last bf16 warp: one thread per 8 channels of a pixel — four 16-B
+// loads, an f32 blend, one 16-B store.  The sample point is
+// (x + scale*fx, y + scale*fy), the scale applied in f32.  flow is read
+// through its element strides (fb, fc, fh, fw), so a 2-channel slice view
+// of a wider channels_last buffer at an odd channel offset is read in place.
+__global__ void bilinear_warp_nhwc_kernel(const uint4* __restrict__ x,
+                                          const __bf16* __restrict__ flow,
+                                          uint4* __restrict__ out, int b,
+                                          int c8, int h, int w, long long fb,
+                                          long long fc, long long fh,
+                                          long long fw, float scale) {
+  const long long total = (long long)b * h * w * c8;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int g = (int)(i % c8);
+    const long long p = i / c8;                 // pixel index over b*h*w
+    const int xx = (int)(p % w);
+    const long long t = p / w;
+    const int yy = (int)(t % h);
+    const int bi = (int)(t / h);
+    const __bf16* fp = flow + bi * fb + yy * fh + xx * fw;
+    const float sx = xx + scale * (float)fp[0];
+    const float sy = yy + scale * (float)fp[fc];
+    const bool inside =
+        (sx >= 0.f) && (sy >= 0.f) && (sx <= w - 1.f) && (sy <= h - 1.f);
+    uint4 o = {0u, 0u, 0u, 0u};
+    if (inside) {
+      const int x0 = (int)floorf(sx), y0 = (int)floorf(sy);
+      const float ax = sx - x0, ay = sy - y0;
+      const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+      const float w00 = (1 - ax) * (1 - ay), w01 = ax * (1 - ay);
+      const float w10 = (1 - ax) * ay, w11 = ax * ay;
+      const uint4* xb = x + (long long)bi * h * w * c8 + g;
+      float v00[8], v01[8], v10[8], v11[8], r[8];
+      bf16x8_to_f32(xb[((long long)y0 * w + x0) * c8], v00);
+      bf16x8_to_f32(xb[((long long)y0 * w + x1) * c8], v01);
+      bf16x8_to_f32(xb[((long long)y1 * w + x0) * c8], v10);
+      bf16x8_to_f32(xb[((long long)y1 * w + x1) * c8], v11);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        r[e] = w00 * v00[e] + w01 * v01[e] + w10 * v10[e] + w11 * v11[e];
+      o = f32_to_bf16x8(r);
+    }
+    out[i] = o;
   }
 }
 
@@ -118,6 +167,21 @@ void vfa_bilinear_warp(const void* x, const void* flow, void* out, int b,
       launch_warp<__hip_bfloat16>(x, flow, out, b, c, h, w, stream); break;
     case VFA_F16: launch_warp<__half>(x, flow, out, b, c, h, w, stream); break;
   }
+}
+
+// x, out: channels_last bf16 (b, c, h, w) with c % 8 == 0; flow: bf16,
+// element strides (fb, fc, fh, fw)
+void vfa_bilinear_warp_nhwc(const void* x, const void* flow, void* out, int b,
+                            int c, int h, int w, long long fb, long long fc,
+                            long long fh, long long fw, float scale,
+                            hipStream_t stream) {
+  const int c8 = c / 8;
+  long long total = (long long)b * h * w * c8;
+  int block = 256;
+  int grid = (int)min((total + block - 1) / block, (long long)8192);
+  hipLaunchKernelGGL(bilinear_warp_nhwc_kernel, dim3(grid), dim3(block), 0,
+                     stream, (const uint4*)x, (const __bf16*)flow,
+                     (uint4*)out, b, c8, h, w, fb, fc, fh, fw, scale);
 }
 
 void vfa_grid_sample(const void* x, const void* coords, void* out,
