@@ -1,6 +1,18 @@
 #!/usr/bin/env python3
 """Microbench: ops.linear_act (fused MFMA GEMM) vs torch F.linear(+act)
-on the CLIP / VGGish / RAFT shapes.  Run on a GPU box."""
+on the CLIP / VGGish / RAFT shapes.  Run on a GPU box.
+
+A row may carry a sixth field, the mode:
+  res        linear_act with a residual operand (torch: F.linear + add)
+  res_stats  ops.linear_res_stats: residual + per-row LayerNorm statistics
+             (torch: F.linear + add, no statistics)
+  ln_act     ops.linear_ln_act on un-normalised rows with a folded weight
+             (torch: F.linear on the already normalised rows)
+After the rows come the LayerNorm-fold chains (CHAINS): what a ViT block
+runs today against the folded pair, each chain replayed from one graph.
+
+VFA_GEMM_GRAPH=1 times every row from a captured graph (kernel time without
+launch gaps); the chains always do."""
 import os
 import sys
 import time
@@ -30,6 +42,14 @@ SHAPES = [
     # fc1's shape without the activation: the difference to the fc1 row is
     # the cost of the fused QuickGELU epilogue
     (19200, 3072, 768, 'none', 'CLIP fc1-noact (fb384)'),
+    (19200, 768, 768, 'none', 'CLIP proj (fb384)'),
+    (19200, 768, 768, 'none', 'CLIP proj+res (fb384)', 'res'),
+    (19200, 768, 3072, 'none', 'CLIP fc2 (fb384)'),
+    (19200, 768, 3072, 'none', 'CLIP fc2+res (fb384)', 'res'),
+    (19200, 768, 768, 'none', 'CLIP proj res_stats (fb384)', 'res_stats'),
+    (19200, 768, 3072, 'none', 'CLIP fc2 res_stats (fb384)', 'res_stats'),
+    (19200, 3072, 768, 'quick_gelu', 'CLIP fc1 ln_act (fb384)', 'ln_act'),
+    (19200, 2304, 768, 'none', 'CLIP qkv ln_act (fb384)', 'ln_act'),
     (1204224, 64, 64, 'relu', 'rn50 l1 conv1 (thin)'),
     (1204224, 256, 64, 'relu', 'rn50 l1 conv3 (thin)'),
     (1204224, 128, 256, 'relu', 'rn50 l2 conv1 (thin)'),
@@ -49,11 +69,40 @@ def timeit(fn, iters=50):
     return (time.perf_counter() - t0) / iters
 
 
+def timeit_graph(fn, iters=50):
+    """Per-call time of fn replayed from a captured graph."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        keep = fn()
+    for _ in range(5):
+        g.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        g.replay()
+    torch.cuda.synchronize()
+    del keep
+    return (time.perf_counter() - t0) / iters
+
+
 # VFA_GEMM_ONLY=substring: run only the rows whose label contains it
 ONLY = os.environ.get('VFA_GEMM_ONLY', '')
+GRAPH = os.environ.get('VFA_GEMM_GRAPH', '') not in ('', '0')
+HAVE_FOLD = hasattr(ops, 'linear_res_stats')
+EPS = 1e-5
 
-for m, n, k, act, label in SHAPES:
+for row in SHAPES:
+    m, n, k, act, label = row[:5]
+    mode = row[5] if len(row) > 5 else 'plain'
     if ONLY and ONLY not in label:
+        continue
+    if mode in ('res_stats', 'ln_act') and not HAVE_FOLD:
         continue
     torch.manual_seed(0)
     # VFA_GEMM_COLD=N: rotate N input buffers so A can't stay resident in
@@ -66,10 +115,27 @@ for m, n, k, act, label in SHAPES:
     w = (torch.randn(n, k, device=dev) / (k ** 0.25)).to(torch.bfloat16)
     b = torch.randn(n, device=dev).to(torch.bfloat16)
     it = [0]
+    res = (torch.randn(m, n, device=dev).to(torch.bfloat16)
+           if mode in ('res', 'res_stats') else None)
+    if mode == 'ln_act':
+        # xs are the un-normalised rows; torch gets them normalised
+        g = torch.randn(k, device=dev).to(torch.bfloat16)
+        be = torch.randn(k, device=dev).to(torch.bfloat16)
+        fold = ops.fold_ln_linear(w, b, g, be)
+        xf = [xi.float() for xi in xs]
+        sts = [torch.stack([xi.mean(1), xi.var(1, unbiased=False) * k], 1)
+               .unsqueeze(1).contiguous() for xi in xf]
+        ys = [torch.nn.functional.layer_norm(xi, (k,), g.float(), be.float(),
+                                             EPS).to(torch.bfloat16)
+              for xi in xf]
+        del xf
 
     def torch_path():
         it[0] += 1
-        y = torch.nn.functional.linear(xs[it[0] % ncold], w, b)
+        src = ys if mode == 'ln_act' else xs
+        y = torch.nn.functional.linear(src[it[0] % ncold], w, b)
+        if res is not None:
+            y = y + res
         if act == 'relu':
             y = y.relu()
         elif act == 'quick_gelu':
@@ -78,21 +144,94 @@ for m, n, k, act, label in SHAPES:
 
     def ours():
         it[0] += 1
-        return ops.linear_act(xs[it[0] % ncold], w, b, act)
+        i = it[0] % ncold
+        if mode == 'res_stats':
+            return ops.linear_res_stats(xs[i], w, b, res)[0]
+        if mode == 'ln_act':
+            return ops.linear_ln_act(xs[i], sts[i], *fold, act, EPS)
+        return ops.linear_act(xs[i], w, b, act, res=res)
 
     flops = 2.0 * m * n * k
-    tt = timeit(torch_path)
-    to = timeit(ours)
+    timer = timeit_graph if GRAPH else timeit
+    tt = timer(torch_path)
+    to = timer(ours)
     # correctness spot-check (same buffer both paths)
-    ref_t = torch.nn.functional.linear(x, w, b)
+    it[0] = -1
+    ref_t = torch.nn.functional.linear(ys[0] if mode == 'ln_act' else x, w, b)
+    if res is not None:
+        ref_t = ref_t + res
     if act == 'relu':
         ref_t = ref_t.relu()
     elif act == 'quick_gelu':
         ref_t = ref_t * torch.sigmoid(1.702 * ref_t)
-    d = (ops.linear_act(x, w, b, act).float()
-         - ref_t.float()).abs().max().item()
+    d = (ours().float() - ref_t.float()).abs().max().item()
     ref = ref_t.float().abs().max().item()
     print(f'{label:<24} M{m:>7} N{n:>5} K{k:>6} {act:<11} '
           f'torch {tt * 1e6:7.1f}us ({flops / tt / 1e12:6.1f} TF) | '
           f'ours {to * 1e6:7.1f}us ({flops / to / 1e12:6.1f} TF) | '
           f'x{tt / to:4.2f} relerr {d / ref:.2e}', flush=True)
+
+
+# ------------------------------------------------------- LayerNorm-fold chains
+# (label, M, width, K1, N2, act2, route of GEMM 2 today): GEMM 1 (M, width,
+# K1) feeds the residual stream, whose LayerNorm feeds GEMM 2 (M, N2, width).
+CHAINS = [
+    ('ln_2 half: proj -> ln_2 -> fc1+QuickGELU (fb384)',
+     19200, 768, 768, 3072, 'quick_gelu', 'in-tree'),
+    ('ln_1 half: fc2 -> ln_1 -> qkv (fb384)',
+     19200, 768, 3072, 2304, 'none', 'hipBLASLt'),
+]
+
+for label, m, wd, k1, n2, act2, gemm2 in CHAINS:
+    if ONLY and ONLY not in label:
+        continue
+    torch.manual_seed(0)
+    x = (torch.randn(m, k1, device=dev) / (k1 ** 0.25)).to(torch.bfloat16)
+    res = torch.randn(m, wd, device=dev).to(torch.bfloat16)
+    w1 = (torch.randn(wd, k1, device=dev) / (k1 ** 0.25)).to(torch.bfloat16)
+    b1 = torch.randn(wd, device=dev).to(torch.bfloat16)
+    w2 = (torch.randn(n2, wd, device=dev) / (wd ** 0.25)).to(torch.bfloat16)
+    b2 = torch.randn(n2, device=dev).to(torch.bfloat16)
+    g = torch.randn(wd, device=dev).to(torch.bfloat16)
+    be = torch.randn(wd, device=dev).to(torch.bfloat16)
+
+    def today():
+        d = torch.nn.functional.linear(x, w1, b1)
+        y, s = ops.layer_norm_residual(d, res, g, be, EPS)
+        if gemm2 == 'in-tree':
+            return ops.linear_act(y, w2, b2, act2), s
+        return torch.nn.functional.linear(y, w2, b2), s
+
+    def parts():
+        return [
+            ('GEMM 1 hipBLASLt',
+             lambda: torch.nn.functional.linear(x, w1, b1)),
+            ('layer_norm_residual',
+             lambda d=torch.nn.functional.linear(x, w1, b1):
+             ops.layer_norm_residual(d, res, g, be, EPS)),
+        ]
+
+    runs = [timeit_graph(today) * 1e6 for _ in range(3)]
+    print(f'{label}\n  today  (hipBLASLt + layer_norm_residual + {gemm2}): '
+          + ' '.join(f'{t:7.1f}' for t in runs) + ' us', flush=True)
+    for name, fn in parts():
+        print(f'    {name:<22} {timeit_graph(fn) * 1e6:7.1f} us', flush=True)
+    if not HAVE_FOLD:
+        continue
+    fold = ops.fold_ln_linear(w2, b2, g, be)
+
+    def folded():
+        s, st = ops.linear_res_stats(x, w1, b1, res)
+        return ops.linear_ln_act(s, st, *fold, act2, EPS), s
+
+    runs = [timeit_graph(folded) * 1e6 for _ in range(3)]
+    print('  folded (linear_res_stats + linear_ln_act):            '
+          + ' '.join(f'{t:7.1f}' for t in runs) + ' us', flush=True)
+    s, st = ops.linear_res_stats(x, w1, b1, res)
+    for name, fn in [
+            ('linear_res_stats', lambda: ops.linear_res_stats(x, w1, b1, res)),
+            ('linear_ln_act', lambda: ops.linear_ln_act(s, st, *fold, act2,
+                                                        EPS))]:
+        print(f'    {name:<22} {timeit_graph(fn) * 1e6:7.1f} us', flush=True)
+    d = (folded()[0].float() - today()[0].float()).abs().max().item()
+    print(f'    max |folded - today| {d:.3e}', flush=True)

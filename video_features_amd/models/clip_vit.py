@@ -20,6 +20,14 @@ and the residual adds — for the [CLS] row of each frame only
 (``VisionTransformer._cls_tail``).  ``VFA_CLIP_FULL_TAIL=1`` runs the last
 block in full instead, for A/B runs and tests; the parameters and
 ``state_dict`` keys are the same either way.
+
+``ln_2`` of the full blocks is not a pass over memory either: ``proj`` adds
+the residual and emits row statistics partials in its GEMM epilogue
+(``ops.linear_res_stats``) and fc1 runs on the un-normalised stream with the
+``ln_2`` affine folded into its weight (``ops.linear_ln_act``).  The folded
+weight is derived state, cached per block and rebuilt when a source
+parameter changes; it is no parameter and no buffer.  ``VFA_NO_LNFOLD=1``
+restores the ``layer_norm_residual`` pass, for A/B runs and tests.
 """
 from __future__ import annotations
 
@@ -60,9 +68,12 @@ class MultiheadSelfAttention(nn.Module):
         self.qkv = nn.Linear(width, 3 * width)
         self.proj = nn.Linear(width, width)
 
+    def heads_out(self, x: torch.Tensor) -> torch.Tensor:
+        """Attention up to, not including, the output projection."""
+        return ops.mhsa_fused(self.qkv(x), self.heads)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        o = ops.mhsa_fused(self.qkv(x), self.heads)
-        return self.proj(o)
+        return self.proj(self.heads_out(x))
 
 
 class MLP(nn.Module):
@@ -76,7 +87,11 @@ class MLP(nn.Module):
         # persistent 256^2 kernel of gemm.hip: 766-793 TF vs 363 TF for
         # hipBLASLt + a separate activation pass at the 384-frame chunk
         # shape, profiles/clip_fc1_epilogue.md); fc2 stays on hipBLASLt,
-        # which wins at K=3072 (919 vs 660 TF)
+        # which wins at K=3072 (919 vs 660 TF).  The full blocks of the
+        # ViT do not come through here: their fc1 is the same kernel on the
+        # un-normalised stream with ln_2 folded in
+        # (ResidualAttentionBlock.attn_mlp_folded,
+        # profiles/clip_ln_fold.md); this is the [CLS] tail's MLP, M = T
         h = ops.linear_act(x, self.c_fc.weight, self.c_fc.bias, 'quick_gelu')
         return self.c_proj(h)
 
@@ -88,11 +103,51 @@ class ResidualAttentionBlock(nn.Module):
         self.attn = MultiheadSelfAttention(width, heads)
         self.ln_2 = LayerNorm(width)
         self.mlp = MLP(width)
+        self._fold = None           # (key, (W', c, b')) of ln_2 -> c_fc
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = x + self.attn(self.ln_1(x))
         x = x + self.mlp(self.ln_2(x))
         return x
+
+    def _ln2_fold(self):
+        """``ops.fold_ln_linear`` of (``mlp.c_fc``, ``ln_2``), built on first
+        use and again whenever one of the four parameters was written in
+        place (``load_state_dict``, ``copy_``: ``_version``) or replaced
+        (``.to()``: ``data_ptr`` / dtype / device)."""
+        src = (self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.ln_2.weight,
+               self.ln_2.bias)
+        key = tuple((p._version, p.data_ptr(), p.dtype, p.device)
+                    for p in src)
+        if self._fold is None or self._fold[0] != key:
+            with torch.no_grad():
+                self._fold = (key, ops.fold_ln_linear(*src))
+        return self._fold[1]
+
+    def fold_routed(self, x: torch.Tensor) -> bool:
+        """Whether ``attn_mlp_folded`` replaces the ``ln_2`` pass for a
+        stream like ``x``: always on the CPU (the ops' torch compositions,
+        same arithmetic as the pass), on the GPU when both GEMMs run their
+        fused kernel — all full 256-row tiles, so not ViT-B/16's 197 tokens
+        at most batch sizes."""
+        if ops._env_flag('VFA_NO_LNFOLD'):
+            return False
+        return not x.is_cuda or (
+            ops.fused_ln_tiles(x, self.attn.proj.weight)
+            and ops.fused_ln_tiles(x, self.mlp.c_fc.weight))
+
+    def attn_mlp_folded(self, y1: torch.Tensor, s1: torch.Tensor):
+        """``ln_1`` output ``y1`` and stream ``s1`` → (MLP delta, stream
+        ``s2 = s1 + attn``), with no ``ln_2`` pass: ``proj`` writes ``s2`` and
+        its row statistics, fc1 + QuickGELU reads ``s2`` through the folded
+        weight."""
+        proj, fc, ln = self.attn.proj, self.mlp.c_fc, self.ln_2
+        s2, st2 = ops.linear_res_stats(self.attn.heads_out(y1), proj.weight,
+                                       proj.bias, s1)
+        h = ops.linear_ln_act(
+            s2, st2, *self._ln2_fold(), act='quick_gelu', eps=ln.eps,
+            unfolded=(fc.weight, fc.bias, ln.weight, ln.bias))
+        return self.mlp.c_proj(h), s2
 
 
 class VisionTransformer(nn.Module):
@@ -144,6 +199,9 @@ class VisionTransformer(nn.Module):
             else:
                 y1, s1 = ops.layer_norm_residual(delta, res, blk.ln_1.weight,
                                                  blk.ln_1.bias, blk.ln_1.eps)
+            if blk.fold_routed(s1):
+                delta, res = blk.attn_mlp_folded(y1, s1)
+                continue
             a = blk.attn(y1)
             y2, s2 = ops.layer_norm_residual(a, s1, blk.ln_2.weight,
                                              blk.ln_2.bias, blk.ln_2.eps)

@@ -575,6 +575,102 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor,
     return _apply_act(y, act)
 
 
+# ------------------------------------------------- LayerNorm folded into GEMMs
+# linear -> (+ residual) -> LayerNorm -> linear without the LayerNorm pass:
+# the first GEMM's epilogue adds the residual and emits row statistics
+# (linear_res_stats), the second runs on the un-normalised rows with the LN
+# affine folded into its weight (fold_ln_linear, linear_ln_act).  The
+# statistics travel as partials, (M, T, 2) f32: for each row the (mean, M2 =
+# Σ (x - mean)²) of T equal-width column groups — one per 256-column tile
+# of the producing GEMM, T = 1 from the torch composition.  The consumer's
+# epilogue merges them (Chan's formula); ln_stats does the same in torch.
+def fused_ln_tiles(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """True when ``linear_res_stats`` / ``linear_ln_act`` of ``x`` (..., K)
+    with ``weight`` (N, K) run their fused kernel: bf16 on the GPU and all
+    full 256x256x64 tiles.  Anything else takes their torch composition."""
+    k, n = x.shape[-1], weight.shape[0]
+    m = x.numel() // max(k, 1)
+    return bool(x.is_cuda and x.dtype == torch.bfloat16
+                and weight.dtype == torch.bfloat16
+                and m > 0 and m % 256 == 0 and n % 256 == 0 and k % 64 == 0
+                and not _env_flag('VFA_NO_LTGEMM') and _use_hip(x))
+
+
+def linear_res_stats(x: torch.Tensor, weight: torch.Tensor,
+                     bias: Optional[torch.Tensor], res: torch.Tensor):
+    """``s = x @ weight^T + bias + res`` and the statistics partials of its
+    rows → (s, stats (M, T, 2) f32), taken from the rounded ``s``.  One
+    persistent MFMA GEMM on the fused route (``fused_ln_tiles``), T = N/256;
+    otherwise ``linear_act`` with the residual and T = 1 in torch."""
+    n = weight.shape[0]
+    if fused_ln_tiles(x, weight):
+        s, stats = _ext.linear_res_stats(
+            x.reshape(-1, x.shape[-1]).contiguous(), weight.contiguous(),
+            bias, res.reshape(-1, n).contiguous())
+        return s.reshape(*x.shape[:-1], n), stats
+    s = linear_act(x, weight, bias, 'none', res)
+    sf = s.reshape(-1, n).float()
+    var, mean = torch.var_mean(sf, dim=1, unbiased=False)
+    return s, torch.stack([mean, var * n], dim=1).unsqueeze(1)
+
+
+def ln_stats(stats: torch.Tensor, n: int, eps: float = 1e-5) -> torch.Tensor:
+    """Statistics partials (M, T, 2) of rows of width ``n`` → (M, 2) rows of
+    LayerNorm (mean, rstd), in the partials' dtype."""
+    gmean, gm2 = stats[..., 0], stats[..., 1]
+    mean = gmean.mean(dim=1, keepdim=True)
+    m2 = (gm2 + (n / stats.shape[1]) * (gmean - mean) ** 2).sum(dim=1)
+    return torch.stack([mean[:, 0], torch.rsqrt(m2 / n + eps)], dim=1)
+
+
+def fold_ln_linear(weight: torch.Tensor, bias: Optional[torch.Tensor],
+                   ln_weight: torch.Tensor, ln_bias: torch.Tensor):
+    """Fold a LayerNorm affine (γ, β) into the linear layer that follows it
+    → (W', c, b') with, for un-normalised rows s with statistics (μ, rstd),
+
+        layer_norm(s) @ W^T + b  =  rstd * (s @ W'^T - μ c) + b'
+
+    W' = γ ⊙ W in the weight's dtype, c[n] = Σ_k W'[n, k] summed from the
+    *rounded* W' (so acc - μ c is Σ (s_k - μ) W'_k whatever μ is), b' = b +
+    W β.  c and b' are f32 (f64 for an f64 weight).  Weights only: computed
+    once per model, not per call."""
+    acc = torch.float64 if weight.dtype == torch.float64 else torch.float32
+    w32 = weight.detach().to(acc)
+    wf = (w32 * ln_weight.detach().to(acc)).to(weight.dtype)
+    c = wf.double().sum(dim=1).to(acc)
+    bf = w32 @ ln_bias.detach().to(acc)
+    if bias is not None:
+        bf = bf + bias.detach().to(acc)
+    return wf.contiguous(), c.contiguous(), bf.contiguous()
+
+
+def linear_ln_act(s: torch.Tensor, stats: torch.Tensor, wf: torch.Tensor,
+                  c: torch.Tensor, bf: torch.Tensor, act: str = 'none',
+                  eps: float = 1e-5, unfolded=None) -> torch.Tensor:
+    """``act(linear(layer_norm(s)))`` from the un-normalised rows ``s``, their
+    statistics partials (``linear_res_stats``) and the folded layer
+    (``fold_ln_linear``): ``act(rstd * (s @ W'^T - μ c) + b')`` in the GEMM
+    epilogue on the fused route, (μ, rstd) merged from the partials there.
+    Off it (``fused_ln_tiles``) the result is ``layer_norm`` then
+    ``linear_act`` with ``unfolded`` = (weight, bias, ln_weight, ln_bias), or
+    the folded formula in torch without it."""
+    n, k = wf.shape
+    if fused_ln_tiles(s, wf):
+        out = _ext.linear_ln_act(s.reshape(-1, k).contiguous(),
+                                 stats.contiguous(), wf.contiguous(), c, bf,
+                                 eps, _act_id(act))
+        return out.reshape(*s.shape[:-1], n)
+    if unfolded is not None:
+        weight, bias, ln_weight, ln_bias = unfolded
+        return linear_act(layer_norm(s, ln_weight, ln_bias, eps), weight,
+                          bias, act)
+    acc = torch.float64 if s.dtype == torch.float64 else torch.float32
+    st = ln_stats(stats.to(acc), k, eps)
+    y = s.reshape(-1, k).to(acc) @ wf.to(acc).t()
+    y = st[:, 1:2] * (y - st[:, 0:1] * c.to(acc)) + bf.to(acc)
+    return _apply_act(y, act).to(s.dtype).reshape(*s.shape[:-1], n)
+
+
 def temporal_merge_fused(y: torch.Tensor, b: int, kt: int, st: int,
                          p0: int, relu: bool = False,
                          p1: Optional[int] = None) -> Optional[torch.Tensor]:

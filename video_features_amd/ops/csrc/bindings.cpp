@@ -58,6 +58,11 @@ void vfa_maxpool3d_same(const void*, void*, long long, int, int, int, int,
 void vfa_maxpool2d_same(const void*, void*, long long, int, int, int, int,
                         int, int, int, int, int, int, int, int, int,
                         hipStream_t);
+void vfa_linear_res_stats(const void*, const void*, const void*, const void*,
+                          void*, void*, int, int, int, hipStream_t);
+void vfa_linear_ln_act(const void*, const void*, int, const void*,
+                       const void*, const void*, void*, int, int, int, float,
+                       int, hipStream_t);
 void vfa_linear_act(const void*, const void*, const void*, const void*,
                     void*, int, int, int, int, hipStream_t);
 void vfa_temporal_merge(const void*, void*, int, int, int, int, int, int,
@@ -554,6 +559,77 @@ torch::Tensor linear_act(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// the fused LayerNorm-fold epilogues exist for full 256^2 tiles only
+static void check_full_tiles(const char* op, int m, int n, int k) {
+  TORCH_CHECK(m > 0 && m % 256 == 0 && n % 256 == 0 && k % 64 == 0, op,
+              ": needs M % 256 == 0, N % 256 == 0, K % 64 == 0, got M=", m,
+              " N=", n, " K=", k);
+}
+
+std::vector<torch::Tensor> linear_res_stats(torch::Tensor x, torch::Tensor w,
+                                            c10::optional<torch::Tensor> bias,
+                                            torch::Tensor res) {
+  // s = x@w^T + b + res (bf16) and stats (M, N/256, 2) f32: per row and
+  // 256-column group the (mean, M2) of the rounded s
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
+              w.scalar_type() == torch::kBFloat16);
+  const int m = (int)x.size(0), kk = (int)x.size(1), n = (int)w.size(0);
+  TORCH_CHECK(w.size(1) == kk);
+  check_full_tiles("linear_res_stats", m, n, kk);
+  const void* bptr = nullptr;
+  torch::Tensor bc;
+  if (bias.has_value()) {
+    bc = bias->contiguous().to(torch::kBFloat16);
+    TORCH_CHECK(bc.numel() == n);
+    bptr = bc.data_ptr();
+  }
+  TORCH_CHECK(res.is_cuda() && res.is_contiguous() &&
+              res.scalar_type() == torch::kBFloat16 &&
+              res.numel() == (long long)m * n,
+              "residual must be (M, N) bf16 contiguous");
+  auto out = torch::empty({m, n}, x.options());
+  auto stats = torch::empty({m, n / 256, 2},
+                            x.options().dtype(torch::kFloat32));
+  vfa_linear_res_stats(x.data_ptr(), w.data_ptr(), bptr, res.data_ptr(),
+                       out.data_ptr(), stats.data_ptr(), m, n, kk,
+                       current_stream());
+  return {out, stats};
+}
+
+torch::Tensor linear_ln_act(torch::Tensor x, torch::Tensor stats,
+                            torch::Tensor w, torch::Tensor ln_c,
+                            torch::Tensor ln_b, double eps, int64_t act) {
+  // act(rstd * (x@w^T - mean * ln_c) + ln_b): x un-normalised rows, w / ln_c
+  // / ln_b the LayerNorm-folded linear layer, stats (M, T, 2) the (mean, M2)
+  // of T equal-width column groups of each row of x
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
+              w.scalar_type() == torch::kBFloat16);
+  const int m = (int)x.size(0), kk = (int)x.size(1), n = (int)w.size(0);
+  TORCH_CHECK(w.size(1) == kk);
+  check_full_tiles("linear_ln_act", m, n, kk);
+  TORCH_CHECK(act >= 0 && act <= 4, "linear_ln_act: unknown activation id ",
+              act);
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() &&
+              stats.scalar_type() == torch::kFloat32 && stats.dim() == 3 &&
+              stats.size(0) == m && stats.size(2) == 2 &&
+              stats.size(1) >= 1 && kk % stats.size(1) == 0,
+              "stats must be (M, T, 2) f32 with K % T == 0");
+  for (const auto* v : {&ln_c, &ln_b})
+    TORCH_CHECK(v->is_cuda() && v->is_contiguous() &&
+                v->scalar_type() == torch::kFloat32 && v->numel() == n,
+                "ln_c / ln_b must be (N) f32");
+  auto out = torch::empty({m, n}, x.options());
+  vfa_linear_ln_act(x.data_ptr(), stats.data_ptr(), (int)stats.size(1),
+                    w.data_ptr(), ln_c.data_ptr(), ln_b.data_ptr(),
+                    out.data_ptr(), m, n, kk, (float)eps, (int)act,
+                    current_stream());
+  return out;
+}
+
 torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
                           c10::optional<torch::Tensor> bias,
                           c10::optional<torch::Tensor> res,
@@ -895,6 +971,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool3d_same", &maxpool3d_same);
   m.def("maxpool2d_same", &maxpool2d_same);
   m.def("linear_act", &linear_act);
+  m.def("linear_res_stats", &linear_res_stats);
+  m.def("linear_ln_act", &linear_ln_act);
   m.def("conv2d_nhwc", &conv2d_nhwc);
   m.def("conv2d_tile", &conv2d_tile);
   m.def("conv_transpose2d_nhwc", &conv_transpose2d_nhwc);

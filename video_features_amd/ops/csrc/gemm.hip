@@ -6,6 +6,12 @@
 //   / none) — the separate activation kernel's full HBM round trip
 //   disappears.
 //
+// Two more entry points run linear256p_kernel with a template mode of its
+// epilogue, for linear -> (+ residual) -> LayerNorm -> linear chains without
+// the LayerNorm pass: vfa_linear_res_stats (residual add + per-row
+// statistics partials out) and vfa_linear_ln_act (LayerNorm folded into the
+// weight, statistics partials in); see epilogue_strips.
+//
 // Kernels, in routing order (launch_linear):
 //   linear_thin_kernel  M-huge / K-shallow streaming (W resident in LDS)
 //   linear256p_kernel   256x256 full tiles, >= 150 of them: persistent
@@ -42,18 +48,120 @@ namespace {
 // fragment write then hit disjoint bank groups, and the read side's 8-col
 // segments stay inside one group.  Wave-local only (lgkmcnt waits, no
 // barrier), so it can run while another tile's glds is in flight.
-template <int ACT, bool HAS_RES>
+//
+// MODE selects what else the epilogue does (linear256p_kernel only):
+//   EPI_STATS  after the bf16 rounding, the (mean, M2) of the row's 64
+//              rounded outputs of this strip.  The 8 lanes lane & 7 hold
+//              one row of the strip, so it is two 8-lane DPP reduces (sum,
+//              then squares about the strip mean: safe for rows whose mean
+//              dwarfs their spread).  The wave's 128 (mean, M2) pairs are
+//              left in its bounce tile ep, as float2 [128]; the kernel
+//              merges the four strips of a tile row and writes one partial
+//              per (row, tile column) — one writer each, no atomics.
+//   EPI_LN     the A rows are un-normalised LayerNorm inputs and W has
+//              the LN affine folded in (ops.fold_ln_linear):
+//              v = rstd * (acc - mean * c[col]) + b'[col], with c, b' f32
+//              vectors; (mean, rstd) of a row come from merging its
+//              x.groups partials, once per tile and row.  bias and res
+//              are not used.
+enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_LN = 2 };
+
+struct EpiExtra {
+  const float* ln_c;        // EPI_LN: c (N), row sums of the folded W
+  const float* ln_b;        // EPI_LN: b' (N)
+  const float2* stats;      // EPI_LN: (M, groups) of (group mean, M2)
+  float2* part;             // EPI_STATS: (M, N/256) of (group mean, M2)
+  int groups;               // EPI_LN: partials per row, K / groups wide each
+  float eps;                // EPI_LN
+};
+
+// sum over the 8 lanes lane & 7 == 0..7, result in all of them: quad_perm
+// [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
+__device__ __forceinline__ float sum8(float v) {
+  auto dpp = [](float x, auto ctrl) {
+    return __builtin_bit_cast(
+        float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x),
+                                           decltype(ctrl)::value, 0xf, 0xf,
+                                           true));
+  };
+  v += dpp(v, std::integral_constant<int, 0xb1>{});
+  v += dpp(v, std::integral_constant<int, 0x4e>{});
+  v += dpp(v, std::integral_constant<int, 0x141>{});
+  return v;
+}
+
+// the value of lane (lane & 7) == j to all 8 lanes of its group: broadcast
+// inside the quads (quad_perm), then the quad that does not hold lane j
+// takes the other quad's (row_half_mirror).  j is a constant after
+// unrolling, so the switch folds.
+__device__ __forceinline__ float bcast8(float v, int j, int l7) {
+  const int i = __builtin_bit_cast(int, v);
+  int b;
+  switch (j & 3) {
+    case 0: b = __builtin_amdgcn_update_dpp(0, i, 0x00, 0xf, 0xf, true); break;
+    case 1: b = __builtin_amdgcn_update_dpp(0, i, 0x55, 0xf, 0xf, true); break;
+    case 2: b = __builtin_amdgcn_update_dpp(0, i, 0xaa, 0xf, 0xf, true); break;
+    default: b = __builtin_amdgcn_update_dpp(0, i, 0xff, 0xf, 0xf, true);
+  }
+  const int m = __builtin_amdgcn_update_dpp(0, b, 0x141, 0xf, 0xf, true);
+  return __builtin_bit_cast(float, (l7 >> 2) == (j >> 2) ? b : m);
+}
+
+template <int ACT, bool HAS_RES, int MODE = EPI_PLAIN>
 __device__ __forceinline__ void epilogue_strips(
     const f32x4 (&acc)[8][4], float* ep, const __bf16* __restrict__ bias,
     const __bf16* __restrict__ res, __bf16* __restrict__ c, int n,
-    long long row0, int col0, int lane) {
+    long long row0, int col0, int lane, const EpiExtra& x = EpiExtra{},
+    int kdim = 0) {
   const int lo = lane & 15, hi4 = lane >> 4;
   const int ec = (lane & 7) * 8;
   const int col = col0 + ec;
-  float bf[8];
+  float bf[8], cf[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) bf[e] = 0.f;
-  if (bias) {
+  for (int e = 0; e < 8; ++e) bf[e] = cf[e] = 0.f;
+  // EPI_LN: 1 / groups and the group width
+  const float gi = MODE == EPI_LN ? 1.f / (float)x.groups : 0.f;
+  const float gw = MODE == EPI_LN ? (float)(kdim / x.groups) : 0.f;
+  const int l7 = lane & 7;
+  // a row's 8 lanes all hold its reduced (mean, M2); lane l7 keeps those
+  // of the two (mi, p) steps with (mi * 2 + p) & 7 == l7
+  float2 sp[2] = {float2{0.f, 0.f}, float2{0.f, 0.f}};
+  // EPI_LN: the same distribution the other way round.  Lane l7 merges the
+  // partials of the rows of those two steps into (mean, rstd) here, once
+  // per tile — Chan's formula for equal-width groups, sums taken about the
+  // first group's mean — and each step fetches its row's pair with bcast8.
+  float2 own[2] = {float2{0.f, 1.f}, float2{0.f, 1.f}};
+  if (MODE == EPI_LN) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const long long r =
+          row0 + h * 64 + (l7 >> 1) * 16 + (l7 & 1) * 8 + (lane >> 3);
+      const float2* pp = x.stats + r * x.groups;
+      const float m0 = pp[0].x;
+      float q = pp[0].y, s1 = 0.f, s2 = 0.f;
+      for (int i = 1; i < x.groups; ++i) {
+        const float2 g = pp[i];
+        const float d = g.x - m0;
+        s1 += d;
+        s2 = fmaf(d, d, s2);
+        q += g.y;
+      }
+      const float m2 = fmaf(gw, s2 - s1 * s1 * gi, q);
+      own[h] = float2{fmaf(s1, gi, m0), rsqrtf(fmaf(m2, gi / gw, x.eps))};
+    }
+  }
+  if (MODE == EPI_LN) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const f32x4 b4 = *reinterpret_cast<const f32x4*>(x.ln_b + col + h * 4);
+      const f32x4 c4 = *reinterpret_cast<const f32x4*>(x.ln_c + col + h * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bf[h * 4 + e] = b4[e];
+        cf[h * 4 + e] = c4[e];
+      }
+    }
+  } else if (bias) {
     const bf16x8 b8 = *reinterpret_cast<const bf16x8*>(bias + col);
 #pragma unroll
     for (int e = 0; e < 8; ++e) bf[e] = (float)b8[e];
@@ -72,19 +180,51 @@ __device__ __forceinline__ void epilogue_strips(
       const float* src = ep + er * 64 + (ec ^ (((er >> 2) & 3) << 4));
       const f32x4 v0 = *reinterpret_cast<const f32x4*>(src);
       const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 4);
-      const long long o = (row0 + mi * 16 + er) * n + col;
+      const long long row = row0 + mi * 16 + er;
+      const long long o = row * n + col;
       bf16x8 rr8{};
       if (HAS_RES) rr8 = *reinterpret_cast<const bf16x8*>(res + o);
+      float2 st{0.f, 1.f};                   // (mean, rstd) of the row
+      if (MODE == EPI_LN) {
+        st.x = bcast8(own[mi >> 2].x, (mi * 2 + p) & 7, l7);
+        st.y = bcast8(own[mi >> 2].y, (mi * 2 + p) & 7, l7);
+      }
       bf16x8 o8;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        float v = (e < 4 ? v0[e & 3] : v1[e & 3]) + bf[e];
+        float v = e < 4 ? v0[e & 3] : v1[e & 3];
+        if (MODE == EPI_LN)
+          v = fmaf(st.y, fmaf(-st.x, cf[e], v), bf[e]);
+        else
+          v += bf[e];
         if (HAS_RES) v += (float)rr8[e];
         o8[e] = (__bf16)act_f(v, ACT);
       }
       *reinterpret_cast<bf16x8*>(c + o) = o8;
+      if (MODE == EPI_STATS) {
+        // from the ROUNDED values: they are what the consumer's MFMAs sum
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += (float)o8[e];
+        const float mean = sum8(s) * (1.f / 64.f);
+        float q = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = (float)o8[e] - mean;
+          q = fmaf(d, d, q);
+        }
+        q = sum8(q);
+        if (((mi * 2 + p) & 7) == l7) sp[mi >> 2] = float2{mean, q};
+      }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);      // reads done before reuse
+  }
+  if (MODE == EPI_STATS) {
+    // step (mi, p) is tile rows mi * 16 + p * 8 + (lane >> 3)
+    float2* ep2 = reinterpret_cast<float2*>(ep) + (l7 >> 1) * 16 +
+                  (l7 & 1) * 8 + (lane >> 3);
+    ep2[0] = sp[0];
+    ep2[64] = sp[1];
   }
 }
 
@@ -205,14 +345,14 @@ void linear_act_kernel(const __bf16* __restrict__ a,
 //    The next tile's first __syncthreads() does the vmcnt(0) drain.
 // No grid-wide synchronisation: blocks are independent, co-residency is
 // not assumed, graph capture is unaffected.
-template <int ACT>
+template <int ACT, int MODE = EPI_PLAIN>
 __global__ __launch_bounds__(512, 1)
 void linear256p_kernel(const __bf16* __restrict__ a,
                        const __bf16* __restrict__ w,
                        const __bf16* __restrict__ bias,
                        const __bf16* __restrict__ res,
                        __bf16* __restrict__ c, int n, int k, int tiles_m,
-                       int ntiles) {
+                       int ntiles, EpiExtra x) {
   constexpr int TILE = 256 * BK * 2;           // one operand, one K-tile
   extern __shared__ __attribute__((aligned(1024))) char smem_p[];
   auto sA = [&](int buf) { return smem_p + buf * (2 * TILE); };
@@ -274,11 +414,42 @@ void linear256p_kernel(const __bf16* __restrict__ a,
 
     const long long row0 = m0 + wm * 128;
     const int col0 = n0 + wn * 64;
-    if (res)
-      epilogue_strips<ACT, true>(acc, ep, bias, res, c, n, row0, col0, lane);
+    if (MODE == EPI_LN)          // no bias / residual operand in this mode
+      epilogue_strips<ACT, false, MODE>(acc, ep, nullptr, nullptr, c, n,
+                                        row0, col0, lane, x, k);
+    else if (res)
+      epilogue_strips<ACT, true, MODE>(acc, ep, bias, res, c, n, row0, col0,
+                                       lane, x);
     else
-      epilogue_strips<ACT, false>(acc, ep, bias, res, c, n, row0, col0,
-                                  lane);
+      epilogue_strips<ACT, false, MODE>(acc, ep, bias, res, c, n, row0,
+                                        col0, lane, x);
+    if (MODE == EPI_STATS) {
+      // the four waves wn of a wave row hold the four 64-column strips of
+      // the tile's rows: merge them (equal counts: mean of the means, M2 =
+      // sum M2_i + 64 * sum (mean_i - mean)^2) into the one partial this
+      // tile owns per row.  LDS only, so the wait is lgkmcnt and the next
+      // tile's prefetch stays in flight; the bounce tiles are written again
+      // only after the next tile's K loop and its barriers.
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_s_barrier();
+      if (threadIdx.x < 256) {
+        const float2* b2 =
+            reinterpret_cast<const float2*>(smem_p + 4 * TILE) +
+            (threadIdx.x >> 7) * 4 * 512 + (threadIdx.x & 127);
+        float2 g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = b2[i * 512];
+        const float mean = 0.25f * ((g[0].x + g[1].x) + (g[2].x + g[3].x));
+        float m2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float d = g[i].x - mean;
+          m2 += fmaf(64.f * d, d, g[i].y);
+        }
+        x.part[(long long)(m0 + (int)threadIdx.x) * (n >> 8) + (n0 >> 8)] =
+            float2{mean, m2};
+      }
+    }
     if (!more) break;
     v = vn; m0 = m0n; n0 = n0n; ap = apn; wp = wpn;
   }
@@ -645,6 +816,34 @@ bool launch_thin(const void* a, const void* w, const void* bias,
   return true;
 }
 
+// the persistent kernel over ntiles full 256^2 tiles (tile columns
+// 0 .. ntiles / tiles_m of an n-wide C), min(ntiles, CUs) blocks
+template <int ACT, int MODE>
+void launch_256p(const void* a, const void* w, const void* bias,
+                 const void* res, void* c, int n, int k, int tiles_m,
+                 int ntiles, const EpiExtra& x, hipStream_t stream) {
+  static const int ncu = [] {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                                dev);
+    return v > 0 ? v : 256;
+  }();
+  constexpr size_t lds_p = 160 * 1024;         // 128 staging + 32 bounce
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&linear256p_kernel<ACT, MODE>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((linear256p_kernel<ACT, MODE>),
+                     dim3((unsigned)min(ntiles, ncu)), dim3(512), lds_p,
+                     stream, (const __bf16*)a, (const __bf16*)w,
+                     (const __bf16*)bias, (const __bf16*)res, (__bf16*)c, n,
+                     k, tiles_m, ntiles, x);
+}
+
 template <int ACT, bool BIG>
 void launch_tile(const void* a, const void* w, const void* bias,
                  const void* res, void* c, int m, int n, int k,
@@ -658,27 +857,9 @@ void launch_tile(const void* a, const void* w, const void* bias,
     // interior tile columns -> the persistent kernel; what is left for
     // the guarded kernel below is at most the ragged last column
     // (n % 8: its 16-B bias/res/out vectors need 8-element row alignment)
-    static const int ncu = [] {
-      int dev = 0, v = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
-                                  dev);
-      return v > 0 ? v : 256;
-    }();
-    constexpr size_t lds_p = 160 * 1024;       // 128 staging + 32 bounce
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&linear256p_kernel<ACT>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-      attr_set = true;
-    }
     const int ntiles = tiles_m * (n / 256);
-    hipLaunchKernelGGL((linear256p_kernel<ACT>),
-                       dim3((unsigned)min(ntiles, ncu)), dim3(512), lds_p,
-                       stream, (const __bf16*)a, (const __bf16*)w,
-                       (const __bf16*)bias, (const __bf16*)res, (__bf16*)c,
-                       n, k, tiles_m, ntiles);
+    launch_256p<ACT, EPI_PLAIN>(a, w, bias, res, c, n, k, tiles_m, ntiles,
+                                EpiExtra{}, stream);
     if (n % 256 == 0) return;
     tile_base = ntiles;
   }
@@ -740,6 +921,40 @@ void vfa_linear_act(const void* a, const void* w, const void* bias,
   // any other id is rejected by the binding
   dispatch_act(act, [&](auto id) {
     launch_linear<decltype(id)::value>(a, w, bias, res, c, m, n, k, stream);
+  });
+}
+
+// s = a @ w^T + bias + res (bf16) and, per row of s and 256-column group
+// (tile column), the (mean, M2) of the rounded values: part (M, N/256)
+// float2.  Full tiles only (m % 256 == n % 256 == k % 64 == 0; the binding
+// checks).
+void vfa_linear_res_stats(const void* a, const void* w, const void* bias,
+                          const void* res, void* c, void* part, int m, int n,
+                          int k, hipStream_t stream) {
+  EpiExtra x{};
+  x.part = (float2*)part;
+  launch_256p<0, EPI_STATS>(a, w, bias, res, c, n, k, m / 256,
+                            (m / 256) * (n / 256), x, stream);
+}
+
+// c = act(rstd * (a @ w^T - mean * ln_c) + ln_b): LayerNorm folded into the
+// linear layer (w, ln_c, ln_b from ops.fold_ln_linear), a un-normalised,
+// stats (M, groups) float2 partials of a's rows over k / groups columns
+// each.  Full tiles only, as above.
+void vfa_linear_ln_act(const void* a, const void* stats, int groups,
+                       const void* w, const void* ln_c, const void* ln_b,
+                       void* c, int m, int n, int k, float eps, int act,
+                       hipStream_t stream) {
+  EpiExtra x{};
+  x.ln_c = (const float*)ln_c;
+  x.ln_b = (const float*)ln_b;
+  x.stats = (const float2*)stats;
+  x.groups = groups;
+  x.eps = eps;
+  dispatch_act(act, [&](auto id) {
+    launch_256p<decltype(id)::value, EPI_LN>(a, w, nullptr, nullptr, c, n, k,
+                                             m / 256, (m / 256) * (n / 256),
+                                             x, stream);
   });
 }
 
