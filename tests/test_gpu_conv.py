@@ -177,3 +177,32 @@ def test_conv2d_mod_downsample_route():
     out = ops.conv2d_act(x, conv.weight, conv.bias, 2, 0, 'none')
     ref = F.conv2d(x.float(), conv.weight.float(), conv.bias.float(), 2, 0)
     assert ((out.float() - ref).abs() / ref.abs().max()).max().item() < 0.08
+
+
+@pytest.mark.parametrize('padding', [1, 0])
+def test_conv2d_mod_1x1_padding(padding, monkeypatch):
+    """A 1x1 module conv with padding keeps its border (the implicit-GEMM
+    kernel; the 1x1 -> GEMM shortcut is for unpadded convs only), and
+    without padding still takes the GEMM.  Small-integer operands: every
+    product and sum is exact, so the result equals the float64 conv."""
+    _hip()
+    dev = 'cuda:0'
+    gen = torch.Generator().manual_seed(0)
+    conv = torch.nn.Conv2d(8, 16, 1, padding=padding)
+    with torch.no_grad():
+        conv.weight.copy_(torch.randint(-3, 4, (16, 8, 1, 1), generator=gen))
+        conv.bias.copy_(torch.randint(-3, 4, (16,), generator=gen))
+    x = torch.randint(-4, 5, (1, 8, 4, 4), generator=gen).double()
+    ref = F.conv2d(x, conv.weight.double(), conv.bias.double(),
+                   padding=padding).to(torch.bfloat16)
+    gemm_calls = []
+    real = ops.conv1x1_act
+    monkeypatch.setattr(ops, 'conv1x1_act', lambda *a, **k: (
+        gemm_calls.append(1), real(*a, **k))[1])
+    conv = conv.to(dev, torch.bfloat16)
+    xg = x.to(dev, torch.bfloat16).contiguous(
+        memory_format=torch.channels_last)
+    out = ops.conv2d_mod(conv, xg)
+    assert out.shape == (1, 16, 4 + 2 * padding, 4 + 2 * padding)
+    assert len(gemm_calls) == (0 if padding else 1)
+    assert torch.equal(out.cpu(), ref)

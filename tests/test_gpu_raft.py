@@ -84,6 +84,16 @@ def test_corr_lookup(dev, nhwc, dtype, tol):
     assert diff < tol, diff
 
 
+def test_corr_lookup_rejects_float64(dev):
+    """An output dtype the kernels do not instantiate raises in the binding
+    (it used to run the fp16 kernel on the 8-byte buffer)."""
+    ops = _hip_loaded()
+    pyr = [torch.zeros(4, 1, 2, 2, device=dev)]
+    coords = torch.zeros(1, 2, 2, 2, device=dev)
+    with pytest.raises(RuntimeError, match='unsupported dtype'):
+        ops.corr_lookup(pyr, coords, 4, False, torch.float64)
+
+
 def test_corr_lookup_gmem_path(dev):
     """Feature maps too large for LDS staging take the global-memory
     kernel; numerics must be identical."""

@@ -60,25 +60,70 @@ def _use_hip(t: torch.Tensor) -> bool:
     return True
 
 
+# the dtypes the dtype-generic kernels instantiate (dispatch_dtype)
+_FLOAT_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def _store_slice(out: Optional[torch.Tensor], out_off: int,
+                 y: torch.Tensor) -> torch.Tensor:
+    """``y`` itself without ``out``; else ``out`` with ``y`` assigned to its
+    channels [out_off, out_off + C_y)."""
+    if out is None:
+        return y
+    out[:, out_off:out_off + y.shape[1]] = y
+    return out
+
+
+def _slice_width(name: str, x: torch.Tensor, in_off: int,
+                 in_ch: Optional[int], aligned: bool = False) -> int:
+    """Channels op ``name`` reads of ``x``: all of them without ``in_ch``,
+    else [in_off, in_off + in_ch).  ``aligned``: the kernels read the slice
+    in place, so it must sit on multiples of 8 inside the buffer."""
+    if in_ch is None:
+        if in_off:
+            raise ValueError(f'{name}: in_off needs in_ch')
+        return x.shape[1]
+    if aligned and (in_off % 8 or x.shape[1] % 8
+                    or in_off + in_ch > x.shape[1]):
+        raise ValueError(
+            f'{name}: slice [{in_off}, {in_off + in_ch}) of a '
+            f'{x.shape[1]}-channel buffer needs in_off and the buffer '
+            'width to be multiples of 8 and the rounded slice inside it')
+    return in_ch
+
+
+def _cached_weight(module: torch.nn.Module, attr: str, key_extra, make):
+    """``make()`` of ``module.weight``, cached on the module as ``attr`` and
+    keyed on the weight's version (a later load_state_dict invalidates),
+    dtype, device, pointer and ``key_extra``."""
+    w = module.weight
+    key = (w._version, w.dtype, w.device, w.data_ptr(), key_extra)
+    ent = getattr(module, attr, None)
+    if ent is None or ent[0] != key:
+        ent = (key, make())
+        setattr(module, attr, ent)
+    return ent[1]
+
+
 # ---------------------------------------------------------------- layernorm
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
                eps: float = 1e-5) -> torch.Tensor:
     """LayerNorm over the last dim. HIP path: one-pass fused kernel
     (vectorized bf16, wave reduction)."""
-    if _use_hip(x) and x.dtype in (torch.bfloat16, torch.float16, torch.float32):
+    if _use_hip(x) and x.dtype in _FLOAT_DTYPES:
         return _ext.layer_norm(x.contiguous(), weight, bias, eps)
     return torch.nn.functional.layer_norm(x, (x.shape[-1],), weight, bias, eps)
 
 
 def quick_gelu(x: torch.Tensor) -> torch.Tensor:
     """CLIP's QuickGELU: x * sigmoid(1.702 x)."""
-    if _use_hip(x) and x.dtype in (torch.bfloat16, torch.float16, torch.float32):
+    if _use_hip(x) and x.dtype in _FLOAT_DTYPES:
         return _ext.quick_gelu(x.contiguous())
     return x * torch.sigmoid(1.702 * x)
 
 
 def gelu(x: torch.Tensor) -> torch.Tensor:
-    if _use_hip(x) and x.dtype in (torch.bfloat16, torch.float16, torch.float32):
+    if _use_hip(x) and x.dtype in _FLOAT_DTYPES:
         return _ext.gelu_tanh(x.contiguous())
     return torch.nn.functional.gelu(x, approximate='tanh')
 
@@ -93,7 +138,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if (_use_hip(q) and q.dtype in (torch.bfloat16, torch.float16, torch.float32)
+    if (_use_hip(q) and q.dtype in _FLOAT_DTYPES
             and q.shape[-2] <= 64 and q.shape[-1] <= 128):
         # fused kernel covers the ViT shapes (N<=64 tokens); longer
         # sequences take the rocBLAS GEMM + softmax path below
@@ -109,7 +154,7 @@ def layer_norm_residual(x: torch.Tensor, res: torch.Tensor,
                         eps: float = 1e-5):
     """Fused ``s = x + res; y = layer_norm(s)`` → (y, s).  One kernel on the
     HIP path (removes the eager add + a full re-read)."""
-    if _use_hip(x) and x.dtype in (torch.bfloat16, torch.float16, torch.float32):
+    if _use_hip(x) and x.dtype in _FLOAT_DTYPES:
         y, s = _ext.layer_norm_residual(x.contiguous(), res.contiguous(),
                                         weight, bias, eps)
         return y, s
@@ -131,7 +176,7 @@ def clip_embed_ln(pe: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor,
     ``VFA_FORCE_TORCH_OPS=1`` take the cat / add / ``layer_norm``
     composition."""
     if (_use_hip(pe) and pe.shape[-1] % 8 == 0
-            and pe.dtype in (torch.bfloat16, torch.float16, torch.float32)):
+            and pe.dtype in _FLOAT_DTYPES):
         return _ext.clip_embed_ln(pe.contiguous(), cls, pos, weight, bias,
                                   eps)
     c = cls.to(pe.dtype).expand(pe.shape[0], 1, -1)
@@ -210,22 +255,17 @@ def pwc_correlation(f1: torch.Tensor, f2: torch.Tensor,
                 and _cl_only(f2)):
             y = _ext.pwc_correlation_nhwc(f1, f2, out if direct else None,
                                           out_off, leaky)
-            if direct:
-                return y
-            out[:, out_off:out_off + y.shape[1]] = y
-            return out
-        y = _ext.pwc_correlation(f1.contiguous(), f2.contiguous(), max_disp,
-                                 out if direct else None, out_off, leaky)
+        else:
+            y = _ext.pwc_correlation(f1.contiguous(), f2.contiguous(),
+                                     max_disp, out if direct else None,
+                                     out_off, leaky)
         if direct:
             return y
     else:
         y = _pwc_correlation_torch(f1, f2, max_disp)
         if leaky:
             y = torch.nn.functional.leaky_relu(y, 0.1)
-    if out is not None:
-        out[:, out_off:out_off + y.shape[1]] = y
-        return out
-    return y
+    return _store_slice(out, out_off, y)
 
 
 def _pwc_correlation_torch(f1: torch.Tensor, f2: torch.Tensor,
@@ -422,22 +462,24 @@ def maxpool2d_same(x: torch.Tensor, kernel, stride,
     ph, pw = _pad1(h, kernel[0], stride[0]), _pad1(w, kernel[1], stride[1])
     if _use_hip(x):
         # resolve the layout defensively: a tensor can be CL-contiguous,
-        # NCHW-contiguous, both (trivial dims), or neither (strided view)
-        if nhwc and not x.is_contiguous(
-                memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        elif not nhwc and not x.is_contiguous():
-            if x.is_contiguous(memory_format=torch.channels_last):
-                nhwc = True
-            else:
-                x = x.contiguous(memory_format=torch.channels_last)
-                nhwc = True
-        out_sz = [(h + ph[0] + ph[1] - kernel[0]) // stride[0] + 1,
-                  (w + pw[0] + pw[1] - kernel[1]) // stride[1] + 1]
-        return _ext.maxpool2d_same(x, list(kernel), list(stride),
-                                   [ph[0], pw[0]], out_sz, nhwc)
+        # NCHW-contiguous, both (trivial dims), or neither (strided view);
+        # what is not NCHW-contiguous runs (converted if need be) as NHWC
+        return _maxpool2d_hip(x, kernel, stride, (ph, pw),
+                              nhwc or not x.is_contiguous())
     xp = torch.nn.functional.pad(x, (pw[0], pw[1], ph[0], ph[1]))
     return torch.nn.functional.max_pool2d(xp, tuple(kernel), tuple(stride))
+
+
+def _maxpool2d_hip(x: torch.Tensor, kernel, stride, pads,
+                   nhwc: bool) -> torch.Tensor:
+    """The max-pool kernel with (before, after) zero ``pads`` of H and W; an
+    ``nhwc`` input that is not channels_last-contiguous is converted."""
+    if nhwc and not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    out_sz = [(n + sum(p) - k) // s + 1
+              for n, p, k, s in zip(x.shape[-2:], pads, kernel, stride)]
+    return _ext.maxpool2d_same(x, list(kernel), list(stride),
+                               [p[0] for p in pads], out_sz, nhwc)
 
 
 def maxpool2d(x: torch.Tensor, kernel, stride, padding,
@@ -447,13 +489,8 @@ def maxpool2d(x: torch.Tensor, kernel, stride, padding,
     torch's NHWC maxpool (which always computes argmax indices) for the
     ResNet stem."""
     if _use_hip(x):
-        h, w = x.shape[-2:]
-        if nhwc and not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        out_sz = [(h + 2 * padding - kernel[0]) // stride[0] + 1,
-                  (w + 2 * padding - kernel[1]) // stride[1] + 1]
-        return _ext.maxpool2d_same(x, list(kernel), list(stride),
-                                   [padding, padding], out_sz, nhwc)
+        return _maxpool2d_hip(x, kernel, stride, [(padding, padding)] * 2,
+                              nhwc)
     return torch.nn.functional.max_pool2d(x, tuple(kernel), tuple(stride),
                                           padding)
 
@@ -724,12 +761,7 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
     """
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
     dh, dw = (dilation, dilation) if isinstance(dilation, int) else dilation
-    if in_ch is None:
-        if in_off:
-            raise ValueError('conv2d_act: in_off needs in_ch')
-        cx = x.shape[1]
-    else:
-        cx = in_ch
+    cx = _slice_width('conv2d_act', x, in_off, in_ch)
     if isinstance(padding, int):
         pt = pb = pl = pr = padding
     elif len(padding) == 2:
@@ -778,21 +810,18 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
                                        (dh, dw))
     if res is not None:
         y = y + res
-    y = _apply_act(y, act)
-    if out is not None:
-        out[:, out_off:out_off + y.shape[1]] = y
-        return out
-    return y
+    return _store_slice(out, out_off, _apply_act(y, act))
 
 
 def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
                res: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None, out_off: int = 0,
                in_off: Optional[int] = None) -> torch.Tensor:
-    """Route an ``nn.Conv2d`` module call through the in-tree kernels:
-    1x1 → fused MFMA GEMM (conv1x1_act), kxk → implicit-GEMM conv
-    (conv2d_act, dilation included); eager composition otherwise (CPU,
-    groups, tiny K_out with C % 8 != 0).
+    """Route an ``nn.Conv2d`` module call through ``conv2d_act`` (which
+    sends an unpadded 1x1 to the fused MFMA GEMM and everything else,
+    dilation included, to the implicit-GEMM conv), with the weight padding
+    its kernels need cached on the module; the module's own forward
+    otherwise (CPU, groups, other dtypes or layouts).
 
     ``out`` / ``out_off``: write the result into channels
     [out_off, out_off + K_out) of the wider buffer ``out`` and return it.
@@ -805,7 +834,6 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
     zero weight columns cancel them.  ``out`` may be ``x`` when the read
     and written slices are disjoint."""
     w = conv.weight
-    kh, kw = w.shape[2], w.shape[3]
     sliced = in_off is not None
     c = conv.in_channels if sliced else x.shape[1]
     c8 = (c + 7) // 8 * 8
@@ -816,63 +844,42 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
                 and hip_available() and not _env_flag('VFA_NO_CONV')
                 and not _env_flag('VFA_FORCE_TORCH_OPS'))
     if eligible and sliced:
-        if in_off % 8 or x.shape[1] % 8 or in_off + c8 > x.shape[1]:
-            raise ValueError(
-                f'conv2d_mod: slice [{in_off}, {in_off + c8}) of a '
-                f'{x.shape[1]}-channel buffer needs in_off and the buffer '
-                'width to be multiples of 8 and the rounded slice inside it')
+        _slice_width('conv2d_mod', x, in_off, c8, aligned=True)
     kw_slice = dict(in_off=in_off, in_ch=c8) if sliced else {}
-    key = (w._version, w.dtype, w.device, w.data_ptr())
+
+    def padded(cpad, npad):
+        return torch.nn.functional.pad(
+            w, (0, 0, 0, 0, 0, cpad, 0, npad)).contiguous(
+                memory_format=torch.channels_last)
+
     if eligible and w.shape[0] < 16 and res is None:
         # tiny-N heads (RAFT flow head N=2, per GRU iteration): pad the
-        # OUTPUT channels to 16 (cached, weight-version-keyed), run
-        # in-tree, slice back.  A slice input also gets its input channels
-        # padded to the slice width.
+        # OUTPUT channels to 16 (cached), run in-tree, slice back.  A slice
+        # input also gets its input channels padded to the slice width.
         kout = w.shape[0]
         cpad = c8 - c if sliced else 0
-        key = key + (cpad,)
-        ent = getattr(conv, '_vfa_wnpad', None)
-        if ent is None or ent[0] != key:
-            wp = torch.nn.functional.pad(
-                w, (0, 0, 0, 0, 0, cpad, 0, 16 - kout)).contiguous(
-                    memory_format=torch.channels_last)
-            bp = (torch.nn.functional.pad(conv.bias, (0, 16 - kout))
-                  if conv.bias is not None else None)
-            conv._vfa_wnpad = ent = (key, wp, bp)
-        y = conv2d_act(x, ent[1], ent[2], conv.stride, conv.padding, act,
-                       dilation=conv.dilation, **kw_slice)
-        if out is not None:
-            out[:, out_off:out_off + kout] = y[:, :kout]
-            return out
-        return y[:, :kout].contiguous(memory_format=torch.channels_last)
-    if eligible and c % 8 != 0:
-        # stems (C=3/2/1) and the RAFT corr input (C=324): zero-pad the
-        # channel dim — weight padded once and cached on the module (keyed
-        # on the weight VERSION so a later load_state_dict invalidates),
-        # input padded inside the conv's (fused) pad pass; a slice input is
-        # read in place at the padded width instead
-        ent = getattr(conv, '_vfa_wpad', None)
-        if ent is None or ent[0] != key:
-            wp = torch.nn.functional.pad(
-                w, (0, 0, 0, 0, 0, c8 - c)).contiguous(
-                    memory_format=torch.channels_last)
-            conv._vfa_wpad = ent = (key, wp)
-        return conv2d_act(x, ent[1], conv.bias, conv.stride, conv.padding,
-                          act, res, out, out_off, conv.dilation, **kw_slice)
-    if eligible and kh == 1 and kw == 1 and conv.stride == (1, 1) \
-            and w.shape[0] % 8 == 0 and not sliced and out is None:
-        return conv1x1_act(x, w, conv.bias, act, res)
+        wp, bp = _cached_weight(conv, '_vfa_wnpad', cpad, lambda: (
+            padded(cpad, 16 - kout),
+            torch.nn.functional.pad(conv.bias, (0, 16 - kout))
+            if conv.bias is not None else None))
+        y = conv2d_act(x, wp, bp, conv.stride, conv.padding, act,
+                       dilation=conv.dilation, **kw_slice)[:, :kout]
+        if out is None:
+            return y.contiguous(memory_format=torch.channels_last)
+        return _store_slice(out, out_off, y)
     if eligible:
-        return conv2d_act(x, w, conv.bias, conv.stride, conv.padding, act,
+        # stems (C=3/2/1) and the RAFT corr input (C=324): the weight's
+        # channel dim is zero-padded once and cached; the input is padded
+        # inside the conv's (fused) pad pass, or, as a slice, read in place
+        # at the padded width
+        wp = w if c % 8 == 0 else _cached_weight(
+            conv, '_vfa_wpad', None, lambda: padded(c8 - c, 0))
+        return conv2d_act(x, wp, conv.bias, conv.stride, conv.padding, act,
                           res, out, out_off, conv.dilation, **kw_slice)
     y = conv(x[:, in_off:in_off + c] if sliced else x)
     if res is not None:
         y = y + res
-    y = _apply_act(y, act)
-    if out is not None:
-        out[:, out_off:out_off + y.shape[1]] = y
-        return out
-    return y
+    return _store_slice(out, out_off, _apply_act(y, act))
 
 
 # ------------------------------------------------- transposed convolution
@@ -952,6 +959,27 @@ def _tconv_out_direct(out: Optional[torch.Tensor]) -> bool:
 _TCONV_MAX_C = 992
 
 
+def _tconv_kernels(x: torch.Tensor, weight: torch.Tensor,
+                   bias: Optional[torch.Tensor],
+                   out: Optional[torch.Tensor], out_off: int, in_off: int,
+                   in_ch: Optional[int], packed) -> Optional[torch.Tensor]:
+    """The tconv.hip route of a call whose geometry, dtype, device and
+    ``out`` the kernels cover: the direct kernel for an unsliced ``x`` of
+    C <= 16, the P-form for a channels_last ``x`` whose slice sits on
+    multiples of 8, with ``packed(width)`` the packed weight; None when the
+    layout fits neither."""
+    cx = x.shape[1] if in_ch is None else in_ch
+    if in_ch is None and cx <= 16:
+        return _ext.conv_transpose2d_small(x, weight.contiguous(), bias, out,
+                                           out_off)
+    if (x.is_contiguous(memory_format=torch.channels_last)
+            and cx % 8 == 0 and in_off % 8 == 0 and x.shape[1] % 8 == 0
+            and cx <= _TCONV_MAX_C):
+        return _ext.conv_transpose2d_nhwc(x, packed(cx), bias, out, out_off,
+                                          in_off, 0 if in_ch is None else in_ch)
+    return None
+
+
 def conv_transpose2d_act(x: torch.Tensor, weight: torch.Tensor,
                          bias: Optional[torch.Tensor] = None,
                          stride=2, padding=1,
@@ -977,31 +1005,18 @@ def conv_transpose2d_act(x: torch.Tensor, weight: torch.Tensor,
     (ValueError).  Without ``out`` the kernel path returns a new
     channels_last (B, K_out, 2H, 2W) tensor.  ``VFA_NO_TCONV=1`` forces
     the composition."""
-    if in_ch is None:
-        if in_off:
-            raise ValueError('conv_transpose2d_act: in_off needs in_ch')
-        cx = x.shape[1]
-    else:
-        cx = in_ch
+    cx = _slice_width('conv_transpose2d_act', x, in_off, in_ch)
     _tconv_check_out(x, out, 'conv_transpose2d_act')
     if (weight.shape[0] == cx and _tconv_out_direct(out)
             and _tconv_kernel_ok(x, weight, stride, padding)):
-        if in_ch is None and cx <= 16:
-            return _ext.conv_transpose2d_small(x, weight.contiguous(), bias,
-                                               out, out_off)
-        if (x.is_contiguous(memory_format=torch.channels_last)
-                and cx % 8 == 0 and in_off % 8 == 0 and x.shape[1] % 8 == 0
-                and cx <= _TCONV_MAX_C):
-            return _ext.conv_transpose2d_nhwc(
-                x, _pack_tconv_weight(weight, cx), bias, out, out_off,
-                in_off, 0 if in_ch is None else in_ch)
+        y = _tconv_kernels(x, weight, bias, out, out_off, in_off, in_ch,
+                           lambda c: _pack_tconv_weight(weight, c))
+        if y is not None:
+            return y
     if in_ch is not None:
         x = x[:, in_off:in_off + in_ch]
     y = torch.nn.functional.conv_transpose2d(x, weight, bias, stride, padding)
-    if out is not None:
-        out[:, out_off:out_off + y.shape[1]] = y
-        return out
-    return y
+    return _store_slice(out, out_off, y)
 
 
 def conv_transpose2d_mod(m: torch.nn.Module, x: torch.Tensor,
@@ -1028,31 +1043,24 @@ def conv_transpose2d_mod(m: torch.nn.Module, x: torch.Tensor,
                 and tuple(m.output_padding) == (0, 0)
                 and c == m.in_channels and _tconv_out_direct(out)
                 and _tconv_kernel_ok(x, w, m.stride, m.padding))
-    if eligible and not sliced and c <= 16:
-        return _ext.conv_transpose2d_small(x, w.contiguous(), m.bias, out,
-                                           out_off)
-    if (eligible and c8 <= _TCONV_MAX_C
-            and x.is_contiguous(memory_format=torch.channels_last)
-            and (sliced or c8 == c)):
-        if sliced and (in_off % 8 or x.shape[1] % 8
-                       or in_off + c8 > x.shape[1]):
-            raise ValueError(
-                f'conv_transpose2d_mod: slice [{in_off}, {in_off + c8}) of '
-                f'a {x.shape[1]}-channel buffer needs in_off and the buffer '
-                'width to be multiples of 8 and the rounded slice inside it')
-        key = (w._version, w.dtype, w.device, w.data_ptr(), c8)
-        ent = getattr(m, '_vfa_tconv_wp', None)
-        if ent is None or ent[0] != key:
-            with torch.no_grad():
-                m._vfa_tconv_wp = ent = (key, _pack_tconv_weight(w, c8))
-        return _ext.conv_transpose2d_nhwc(x, ent[1], m.bias, out, out_off,
-                                          in_off if sliced else 0,
-                                          c8 if sliced else 0)
+    if eligible:
+        if (sliced and c8 <= _TCONV_MAX_C
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            _slice_width('conv_transpose2d_mod', x, in_off, c8, aligned=True)
+
+        def packed(width):
+            def make():
+                with torch.no_grad():
+                    return _pack_tconv_weight(w, width)
+            return _cached_weight(m, '_vfa_tconv_wp', width, make)
+
+        y = _tconv_kernels(x, w, m.bias, out, out_off,
+                           in_off if sliced else 0, c8 if sliced else None,
+                           packed)
+        if y is not None:
+            return y
     y = m(x[:, in_off:in_off + c] if sliced else x)
-    if out is not None:
-        out[:, out_off:out_off + y.shape[1]] = y
-        return out
-    return y
+    return _store_slice(out, out_off, y)
 
 
 def grid_sample_bilinear(x: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:

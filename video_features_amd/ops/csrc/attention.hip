@@ -91,11 +91,8 @@ void launch_mhsa(const void* q, const void* k, const void* v, void* out,
 extern "C" void vfa_mhsa_small(const void* q, const void* k, const void* v,
                                void* out, int bh, int n, int d, float scale,
                                int dtype, hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_mhsa<float>(q, k, v, out, bh, n, d, scale, stream); break;
-    case VFA_BF16:
-      launch_mhsa<__hip_bfloat16>(q, k, v, out, bh, n, d, scale, stream); break;
-    case VFA_F16:
-      launch_mhsa<__half>(q, k, v, out, bh, n, d, scale, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_mhsa<typename decltype(t)::type>(q, k, v, out, bh, n, d, scale,
+                                            stream);
+  });
 }

@@ -1,6 +1,7 @@
 // Python bindings for the VFA gfx950 HIP kernels (torch extension ABI).
-// Kernels live in the sibling .hip TUs behind a C ABI so this (slow,
-// torch-header-heavy) TU rarely recompiles.
+// Kernels live in the sibling .hip TUs behind a C ABI (vfa_api.h, the one
+// declaration both sides compile against) so this slow, torch-header-heavy
+// TU stays apart from the device code.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <mutex>
@@ -8,97 +9,79 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-extern "C" {
-void vfa_quick_gelu(const void*, void*, long long, int, hipStream_t);
-void vfa_gelu_tanh(const void*, void*, long long, int, hipStream_t);
-void vfa_layer_norm(const void*, const void*, const void*, void*, long long,
-                    int, float, int, hipStream_t);
-void vfa_bilinear_warp(const void*, const void*, void*, int, int, int, int,
-                       int, hipStream_t);
-void vfa_bilinear_warp_nhwc(const void*, const void*, void*, int, int, int,
-                            int, long long, long long, long long, long long,
-                            float, hipStream_t);
-void vfa_pwc_correlation_nhwc(const void*, const void*, void*, int, int, int,
-                              int, int, int, hipStream_t);
-long long vfa_tconv_lds_bytes(int, int);
-void vfa_tconv_pform(const void*, const void*, const void*, void*, void*, int,
-                     int, int, int, int, int, int, hipStream_t);
-void vfa_tconv_direct(const void*, const void*, const void*, void*, int, int,
-                      int, int, long long, long long, long long, long long,
-                      int, int, hipStream_t);
-void vfa_grid_sample(const void*, const void*, void*, long long, int, int,
-                     int, int, int, int, hipStream_t);
-void vfa_corr_repack(const void*, void*, int, int, int, int, int,
-                     hipStream_t);
-void vfa_pwc_correlation(const void*, const void*, const void*, void*, int,
-                         int, int, int, int, int, int, hipStream_t);
-void vfa_mhsa_small(const void*, const void*, const void*, void*, int, int,
-                    int, float, int, hipStream_t);
-void vfa_flash_qkv(const void*, void*, int, int, int, float, hipStream_t);
-void vfa_mfma_gemm16(const void*, const void*, void*, hipStream_t);
-void vfa_layer_norm_residual(const void*, const void*, const void*,
-                             const void*, void*, void*, long long, int,
-                             float, int, hipStream_t);
-void vfa_u8_chw_norm(const void*, void*, long long, int, int, const float*,
-                     const float*, int, hipStream_t);
-void vfa_corr_lookup(const void*, const void*, const void*, const void*,
-                     const void*, void*, int, int, int, int, int, int, int,
-                     int, int, long long, int, int, int, int, hipStream_t);
-void vfa_convex_upsample(const void*, const void*, void*, int, int, int, int,
-                         int, hipStream_t);
-void vfa_gru_zr(const void*, const void*, void*, void*, int, int, int,
-                long long, int, int, hipStream_t);
-void vfa_gru_out(const void*, const void*, void*, int, int, int, long long,
-                 int, int, hipStream_t);
-void vfa_instance_norm2d(const void*, void*, int, int, int, float, int, int,
-                         int, hipStream_t);
-void vfa_maxpool3d_same(const void*, void*, long long, int, int, int, int,
-                        int, int, int, int, int, int, int, int, int, int,
-                        int, int, hipStream_t);
-void vfa_maxpool2d_same(const void*, void*, long long, int, int, int, int,
-                        int, int, int, int, int, int, int, int, int,
-                        hipStream_t);
-void vfa_linear_res_stats(const void*, const void*, const void*, const void*,
-                          void*, void*, int, int, int, hipStream_t);
-void vfa_linear_ln_act(const void*, const void*, int, const void*,
-                       const void*, const void*, void*, int, int, int, float,
-                       int, hipStream_t);
-void vfa_linear_act(const void*, const void*, const void*, const void*,
-                    void*, int, int, int, int, hipStream_t);
-void vfa_temporal_merge(const void*, void*, int, int, int, int, int, int,
-                        int, long long, int, int, hipStream_t);
-void vfa_conv2d_nhwc(const void*, const void*, const void*, const void*,
-                     const void*, void*, int, int, int, int, int, int, int,
-                     int, int, int, int, int, int, int, int, int, int, int,
-                     hipStream_t);
-void vfa_conv2d_pick_tile(int, int, int*, int*);
-void vfa_pad2d_nhwc(const void*, void*, int, int, int, int, int, int, int,
-                    int, int, hipStream_t);
-void vfa_avgpool2d_nhwc(const void*, void*, long long, int, int, int, int,
-                        int, int, hipStream_t);
-void vfa_attnpool_tokens(const void*, const void*, void*, long long, int, int,
-                         hipStream_t);
-void vfa_attention_pool_d64(const void*, const void*, void*, long long, int,
-                            int, float, hipStream_t);
-void vfa_clip_embed_ln(const void*, const void*, const void*, const void*,
-                       const void*, void*, long long, int, int, float, int,
-                       hipStream_t);
-}
+#include "vfa_api.h"
 
 namespace {
 
-int dtype_tag(const torch::Tensor& t) {
-  switch (t.scalar_type()) {
+int dtype_tag(torch::ScalarType s) {
+  switch (s) {
     case torch::kFloat32: return 0;
     case torch::kBFloat16: return 1;
     case torch::kFloat16: return 2;
     default:
-      TORCH_CHECK(false, "unsupported dtype ", t.scalar_type());
+      TORCH_CHECK(false, "unsupported dtype ", s);
   }
 }
 
+int dtype_tag(const torch::Tensor& t) { return dtype_tag(t.scalar_type()); }
+
 hipStream_t current_stream() {
   return c10::hip::getCurrentHIPStream().stream();
+}
+
+// channels_last strides (a tensor with C == 1 or H == W == 1 is both)
+bool cl_contig(const torch::Tensor& t) {
+  return t.is_contiguous(torch::MemoryFormat::ChannelsLast);
+}
+
+// 4-D, channels_last and NOT also plain contiguous
+bool cl_only(const torch::Tensor& t) {
+  return t.dim() == 4 && cl_contig(t) && !t.is_contiguous();
+}
+
+// the layout an op's nhwc flag promises for t
+void check_layout(const torch::Tensor& t, bool nhwc) {
+  TORCH_CHECK(nhwc ? cl_contig(t) : t.is_contiguous(),
+              nhwc ? "channels_last expected" : "contiguous expected");
+}
+
+// (b, c, h, w) view of newly allocated NHWC memory
+torch::Tensor empty_nhwc(int64_t b, int64_t c, int64_t h, int64_t w,
+                         const torch::TensorOptions& opts) {
+  return torch::empty({b, h, w, c}, opts).permute({0, 3, 1, 2});
+}
+
+// optional bias of n elements as contiguous bf16: (keep-alive, pointer or
+// nullptr)
+std::pair<torch::Tensor, const void*> bf16_bias(
+    const c10::optional<torch::Tensor>& bias, int64_t n) {
+  if (!bias.has_value()) return {torch::Tensor(), nullptr};
+  auto bc = bias->contiguous().to(torch::kBFloat16);
+  TORCH_CHECK(bc.numel() == n, "bias must have ", n, " elements");
+  return {bc, bc.data_ptr()};
+}
+
+// Where a kernel writes its k NHWC bf16 output channels: the channel slice
+// [out_off, out_off + k) of out_buf, a channels_last bf16 (b, >= out_off + k,
+// oh, ow) buffer, or a new channels_last (b, k, oh, ow) tensor.  Returns
+// (tensor, first slice element, pixel stride in elements).  Any rule about
+// out_buf overlapping an input is the caller's.
+std::tuple<torch::Tensor, void*, int> out_slice(
+    const c10::optional<torch::Tensor>& out_buf, int64_t out_off, int64_t b,
+    int64_t k, int64_t oh, int64_t ow, const torch::TensorOptions& opts) {
+  if (!out_buf.has_value()) {
+    auto out = empty_nhwc(b, k, oh, ow, opts);
+    return {out, out.data_ptr(), (int)k};
+  }
+  auto out = *out_buf;
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && cl_contig(out) &&
+              out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
+              out.size(2) == oh && out.size(3) == ow && out_off >= 0 &&
+              out_off + k <= out.size(1),
+              "out buffer must be channels_last bf16 (B, >= out_off + ", k,
+              ", ", oh, ", ", ow, ")");
+  return {out, static_cast<char*>(out.data_ptr()) + out_off * 2,
+          (int)out.size(1)};
 }
 
 torch::Tensor quick_gelu(torch::Tensor x) {
@@ -166,12 +149,6 @@ torch::Tensor bilinear_warp(torch::Tensor x, torch::Tensor flow) {
   return out;
 }
 
-bool cl_only(const torch::Tensor& t) {
-  return t.dim() == 4 &&
-         t.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
-         !t.is_contiguous();
-}
-
 // x channels_last bf16 (C % 8 == 0); flow bf16 (B, 2, H, W) of ANY strides,
 // read in place; sample point (x + scale*fx, y + scale*fy); channels_last
 // result
@@ -211,23 +188,10 @@ torch::Tensor pwc_correlation_nhwc(torch::Tensor f1, torch::Tensor f2,
               "corr_wave registers cover C<=256 (PWC max is 196)");
   const int b = (int)f1.size(0), c = (int)f1.size(1);
   const int h = (int)f1.size(2), w = (int)f1.size(3);
-  torch::Tensor out;
-  if (out_buf.has_value()) {
-    out = *out_buf;
-    TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
-                out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
-                out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
-                out.size(2) == h && out.size(3) == w && out_off >= 0 &&
-                out_off + 81 <= out.size(1),
-                "out buffer must be CL bf16 (B, >=off+81, H, W)");
-  } else {
-    out_off = 0;
-    out = torch::empty({b, h, w, 81}, f1.options()).permute({0, 3, 1, 2});
-  }
-  vfa_pwc_correlation_nhwc(f1.data_ptr(), f2.data_ptr(),
-                           static_cast<char*>(out.data_ptr()) + out_off * 2,
-                           b, c, h, w, (int)out.size(1), leaky ? 1 : 0,
-                           current_stream());
+  auto [out, optr, ldo] = out_slice(out_buf, out_off, b, 81, h, w,
+                                    f1.options());
+  vfa_pwc_correlation_nhwc(f1.data_ptr(), f2.data_ptr(), optr, b, c, h, w,
+                           ldo, leaky ? 1 : 0, current_stream());
   return out;
 }
 
@@ -268,17 +232,9 @@ torch::Tensor pwc_correlation(torch::Tensor f1, torch::Tensor f2,
   if (c > 64) vfa_corr_repack(f1.data_ptr(), f1p.data_ptr(), b, c, h, w, tag, stream);
   vfa_corr_repack(f2.data_ptr(), f2p.data_ptr(), b, c, h, w, tag, stream);
   if (out_buf.has_value()) {
-    auto out = *out_buf;
-    TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
-                out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
-                out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
-                out.size(2) == h && out.size(3) == w && out_off >= 0 &&
-                out_off + 81 <= out.size(1),
-                "out buffer must be CL bf16 (B, >=off+81, H, W)");
-    vfa_pwc_correlation(f1.data_ptr(), f1p.data_ptr(), f2p.data_ptr(),
-                        static_cast<char*>(out.data_ptr()) + out_off * 2, b,
-                        c, h, w, tag, (int)out.size(1), leaky ? 1 : 0,
-                        stream);
+    auto [out, optr, ldo] = out_slice(out_buf, out_off, b, 81, h, w, opts);
+    vfa_pwc_correlation(f1.data_ptr(), f1p.data_ptr(), f2p.data_ptr(), optr,
+                        b, c, h, w, tag, ldo, leaky ? 1 : 0, stream);
     return out;
   }
   auto out = torch::empty({b, 81, h, w}, opts.dtype(torch::kFloat32));
@@ -372,46 +328,36 @@ torch::Tensor corr_lookup(std::vector<torch::Tensor> pyramid,
   // (contiguous, or channels_last when nhwc) in out_dtype.
   const int levels = (int)pyramid.size();
   TORCH_CHECK(levels >= 1 && levels <= 4, "1..4 pyramid levels");
+  const int tag = dtype_tag(out_dtype);   // raises before anything launches
   TORCH_CHECK(coords.is_cuda() && coords.dim() == 4 && coords.size(1) == 2);
   auto cc = coords.to(torch::kFloat32).contiguous();
   const long long b = coords.size(0);
   const int h = (int)coords.size(2), w = (int)coords.size(3);
   const long long npix = b * h * w;
-  int hs[4] = {1, 1, 1, 1}, ws[4] = {1, 1, 1, 1};
-  const void* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
+  CorrPyramid pyr;
   long long lds_floats = 0;
   for (int l = 0; l < levels; ++l) {
     auto& t = pyramid[l];
     TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
                 t.scalar_type() == torch::kFloat32);
     TORCH_CHECK(t.size(0) == npix && t.size(1) == 1, "plane-per-pixel");
-    hs[l] = (int)t.size(2);
-    ws[l] = (int)t.size(3);
-    ptrs[l] = t.data_ptr();
-    lds_floats += hs[l] * ws[l];
+    pyr.hs[l] = (int)t.size(2);
+    pyr.ws[l] = (int)t.size(3);
+    pyr.lvl[l] = t.data_ptr();
+    lds_floats += pyr.hs[l] * pyr.ws[l];
   }
-  for (int l = levels; l < 4; ++l) ptrs[l] = ptrs[levels - 1];
+  for (int l = levels; l < 4; ++l) {
+    pyr.hs[l] = pyr.ws[l] = 1;
+    pyr.lvl[l] = pyr.lvl[levels - 1];
+  }
   const int ctot = levels * 81;
   auto opts = coords.options().dtype(out_dtype);
-  torch::Tensor out;
-  if (nhwc) {
-    out = torch::empty({b, h, w, ctot}, opts)
-              .permute({0, 3, 1, 2});  // memory is NHWC; view as NCHW
-  } else {
-    out = torch::empty({b, ctot, h, w}, opts);
-  }
-  int tag = out_dtype == torch::kFloat32 ? 0
-            : out_dtype == torch::kBFloat16 ? 1 : 2;
-  vfa_corr_lookup(ptrs[0], ptrs[1], ptrs[2], ptrs[3], cc.data_ptr(),
-                  out.data_ptr(), levels, hs[0], ws[0], hs[1], ws[1], hs[2],
-                  ws[2], hs[3], ws[3], npix, h * w,
+  auto out = nhwc ? empty_nhwc(b, ctot, h, w, opts)
+                  : torch::empty({b, ctot, h, w}, opts);
+  vfa_corr_lookup(pyr, cc.data_ptr(), out.data_ptr(), levels, npix, h * w,
                   (int)((lds_floats <= 16384 && !force_gmem) ? lds_floats : 0),
                   nhwc ? 1 : 0, tag, current_stream());
   return out;
-}
-
-static bool cl_contig(const torch::Tensor& t) {
-  return t.is_contiguous(torch::MemoryFormat::ChannelsLast);
 }
 
 torch::Tensor convex_upsample(torch::Tensor flow, torch::Tensor mask,
@@ -419,11 +365,8 @@ torch::Tensor convex_upsample(torch::Tensor flow, torch::Tensor mask,
   TORCH_CHECK(flow.is_cuda() && flow.dim() == 4 && flow.size(1) == 2);
   TORCH_CHECK(mask.dim() == 4 && mask.size(1) == 576);
   TORCH_CHECK(mask.scalar_type() == flow.scalar_type());
-  if (nhwc) {
-    TORCH_CHECK(cl_contig(flow) && cl_contig(mask), "channels_last expected");
-  } else {
-    TORCH_CHECK(flow.is_contiguous() && mask.is_contiguous());
-  }
+  check_layout(flow, nhwc);
+  check_layout(mask, nhwc);
   const int b = (int)flow.size(0), h = (int)flow.size(2),
             w = (int)flow.size(3);
   auto out = torch::empty({b, 2, 8 * h, 8 * w}, flow.options());
@@ -439,16 +382,9 @@ torch::Tensor gru_zr(torch::Tensor zr, torch::Tensor hx, torch::Tensor rhx,
   const int b = (int)zr.size(0), c2 = (int)zr.size(1);
   const int c = c2 / 2, ctot = (int)hx.size(1);
   const long long hw = (long long)zr.size(2) * zr.size(3);
-  if (nhwc) {
-    TORCH_CHECK(cl_contig(zr) && cl_contig(hx) && cl_contig(rhx));
-  } else {
-    TORCH_CHECK(zr.is_contiguous() && hx.is_contiguous() &&
-                rhx.is_contiguous());
-  }
-  auto z = nhwc ? torch::empty({b, (int)zr.size(2), (int)zr.size(3), c},
-                               zr.options()).permute({0, 3, 1, 2})
-                : torch::empty({b, c, (int)zr.size(2), (int)zr.size(3)},
-                               zr.options());
+  for (const auto* t : {&zr, &hx, &rhx}) check_layout(*t, nhwc);
+  auto z = nhwc ? empty_nhwc(b, c, zr.size(2), zr.size(3), zr.options())
+                : torch::empty({b, c, zr.size(2), zr.size(3)}, zr.options());
   vfa_gru_zr(zr.data_ptr(), hx.data_ptr(), rhx.data_ptr(), z.data_ptr(), b,
              c, ctot - c, hw, nhwc ? 1 : 0, dtype_tag(zr), current_stream());
   return z;
@@ -457,11 +393,8 @@ torch::Tensor gru_zr(torch::Tensor zr, torch::Tensor hx, torch::Tensor rhx,
 void gru_out(torch::Tensor q, torch::Tensor z, torch::Tensor hx, bool nhwc) {
   const int b = (int)q.size(0), c = (int)q.size(1), ctot = (int)hx.size(1);
   const long long hw = (long long)q.size(2) * q.size(3);
-  if (nhwc) {
-    TORCH_CHECK(cl_contig(q) && cl_contig(hx));
-  } else {
-    TORCH_CHECK(q.is_contiguous() && hx.is_contiguous());
-  }
+  check_layout(q, nhwc);
+  check_layout(hx, nhwc);
   vfa_gru_out(q.data_ptr(), z.data_ptr(), hx.data_ptr(), b, c, ctot - c, hw,
               nhwc ? 1 : 0, dtype_tag(q), current_stream());
 }
@@ -469,17 +402,32 @@ void gru_out(torch::Tensor q, torch::Tensor z, torch::Tensor hx, bool nhwc) {
 torch::Tensor instance_norm2d(torch::Tensor x, double eps, bool relu,
                               bool nhwc) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4);
-  if (nhwc) {
-    TORCH_CHECK(cl_contig(x), "channels_last expected");
-  } else {
-    TORCH_CHECK(x.is_contiguous());
-  }
+  check_layout(x, nhwc);
   auto out = torch::empty_like(x);
   vfa_instance_norm2d(x.data_ptr(), out.data_ptr(), (int)x.size(0),
                       (int)x.size(1), (int)(x.size(2) * x.size(3)),
                       (float)eps, relu ? 1 : 0, nhwc ? 1 : 0, dtype_tag(x),
                       current_stream());
   return out;
+}
+
+// nd = 2 or 3 pooled dims: the last nd of x
+PoolGeom pool_geom(const torch::Tensor& x, int nd,
+                   const std::vector<int64_t>& kernel,
+                   const std::vector<int64_t>& stride,
+                   const std::vector<int64_t>& pad_front,
+                   const std::vector<int64_t>& out_sz) {
+  for (const auto* v : {&kernel, &stride, &pad_front, &out_sz})
+    TORCH_CHECK((int)v->size() >= nd, "pool: ", nd, " values per argument");
+  PoolGeom g{};
+  for (int i = 0; i < nd; ++i) {
+    g.in[i] = (int)x.size(x.dim() - nd + i);
+    g.out[i] = (int)out_sz[i];
+    g.k[i] = (int)kernel[i];
+    g.s[i] = (int)stride[i];
+    g.pad[i] = (int)pad_front[i];
+  }
+  return g;
 }
 
 torch::Tensor maxpool3d_same(torch::Tensor x, std::vector<int64_t> kernel,
@@ -490,13 +438,9 @@ torch::Tensor maxpool3d_same(torch::Tensor x, std::vector<int64_t> kernel,
   const long long bc = x.size(0) * x.size(1);
   auto out = torch::empty({x.size(0), x.size(1), out_sz[0], out_sz[1],
                            out_sz[2]}, x.options());
-  vfa_maxpool3d_same(x.data_ptr(), out.data_ptr(), bc, (int)x.size(2),
-                     (int)x.size(3), (int)x.size(4), (int)out_sz[0],
-                     (int)out_sz[1], (int)out_sz[2], (int)kernel[0],
-                     (int)kernel[1], (int)kernel[2], (int)stride[0],
-                     (int)stride[1], (int)stride[2], (int)pad_front[0],
-                     (int)pad_front[1], (int)pad_front[2], dtype_tag(x),
-                     current_stream());
+  vfa_maxpool3d_same(x.data_ptr(), out.data_ptr(), bc,
+                     pool_geom(x, 3, kernel, stride, pad_front, out_sz),
+                     dtype_tag(x), current_stream());
   return out;
 }
 
@@ -505,22 +449,14 @@ torch::Tensor maxpool2d_same(torch::Tensor x, std::vector<int64_t> kernel,
                              std::vector<int64_t> pad_front,
                              std::vector<int64_t> out_sz, bool nhwc) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4);
-  if (nhwc) {
-    TORCH_CHECK(cl_contig(x), "channels_last expected");
-  } else {
-    TORCH_CHECK(x.is_contiguous());
-  }
+  check_layout(x, nhwc);
   auto out = nhwc
-      ? torch::empty({x.size(0), out_sz[0], out_sz[1], x.size(1)},
-                     x.options()).permute({0, 3, 1, 2})
+      ? empty_nhwc(x.size(0), x.size(1), out_sz[0], out_sz[1], x.options())
       : torch::empty({x.size(0), x.size(1), out_sz[0], out_sz[1]},
                      x.options());
-  vfa_maxpool2d_same(x.data_ptr(), out.data_ptr(), x.size(0),
-                     (int)x.size(1), (int)x.size(2), (int)x.size(3),
-                     (int)out_sz[0], (int)out_sz[1], (int)kernel[0],
-                     (int)kernel[1], (int)stride[0], (int)stride[1],
-                     (int)pad_front[0], (int)pad_front[1], nhwc ? 1 : 0,
-                     dtype_tag(x), current_stream());
+  vfa_maxpool2d_same(x.data_ptr(), out.data_ptr(), x.size(0), (int)x.size(1),
+                     pool_geom(x, 2, kernel, stride, pad_front, out_sz),
+                     nhwc ? 1 : 0, dtype_tag(x), current_stream());
   return out;
 }
 
@@ -538,13 +474,7 @@ torch::Tensor linear_act(torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(w.size(1) == kk && kk % 8 == 0, "K%8==0 required");
   TORCH_CHECK(act >= 0 && act <= 4, "linear_act: unknown activation id ",
               act);
-  const void* bptr = nullptr;
-  torch::Tensor bc;
-  if (bias.has_value()) {
-    bc = bias->contiguous().to(torch::kBFloat16);
-    TORCH_CHECK(bc.numel() == n);
-    bptr = bc.data_ptr();
-  }
+  auto [bc, bptr] = bf16_bias(bias, n);
   const void* rptr = nullptr;
   if (res.has_value()) {
     TORCH_CHECK(res->is_contiguous() &&
@@ -578,13 +508,7 @@ std::vector<torch::Tensor> linear_res_stats(torch::Tensor x, torch::Tensor w,
   const int m = (int)x.size(0), kk = (int)x.size(1), n = (int)w.size(0);
   TORCH_CHECK(w.size(1) == kk);
   check_full_tiles("linear_res_stats", m, n, kk);
-  const void* bptr = nullptr;
-  torch::Tensor bc;
-  if (bias.has_value()) {
-    bc = bias->contiguous().to(torch::kBFloat16);
-    TORCH_CHECK(bc.numel() == n);
-    bptr = bc.data_ptr();
-  }
+  auto [bc, bptr] = bf16_bias(bias, n);
   TORCH_CHECK(res.is_cuda() && res.is_contiguous() &&
               res.scalar_type() == torch::kBFloat16 &&
               res.numel() == (long long)m * n,
@@ -683,10 +607,9 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
   const bool inline_pad = (c8 == c);
   torch::Tensor xp = x;
   if (!inline_pad && (pt > 0 || pb > 0 || pl > 0 || pr > 0 || c8 != c)) {
-    xp = torch::empty({b, hp, wp, c8}, x.options());
+    xp = empty_nhwc(b, c8, hp, wp, x.options());
     vfa_pad2d_nhwc(x.data_ptr(), xp.data_ptr(), b, h, ww, c, c8, (int)pt,
                    (int)pb, (int)pl, (int)pr, stream);
-    xp = xp.permute({0, 3, 1, 2});   // logical NCHW view, CL physical
   }
   // 1 KiB zero page for out-of-image glds redirects (per device, cached)
   static std::unordered_map<int, torch::Tensor> zpages;
@@ -702,13 +625,7 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
       zpage = it->second;
     }
   }
-  const void* bptr = nullptr;
-  torch::Tensor bc;
-  if (bias.has_value()) {
-    bc = bias->contiguous().to(torch::kBFloat16);
-    TORCH_CHECK(bc.numel() == kout);
-    bptr = bc.data_ptr();
-  }
+  auto [bc, bptr] = bf16_bias(bias, kout);
   const void* rptr = nullptr;
   if (res.has_value()) {
     TORCH_CHECK(cl_contig(*res) && res->scalar_type() == torch::kBFloat16 &&
@@ -719,17 +636,9 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
   // optional preallocated WIDER output buffer: the epilogue writes the
   // channel slice [out_off, out_off + kout) of a (B, C_total, OH, OW) CL
   // tensor (eliminates a following cat copy)
-  torch::Tensor out;
-  int ldc = kout;
-  void* optr;
+  auto [out, optr, ldc] = out_slice(out_buf, out_off, b, kout, oh, ow,
+                                    x.options());
   if (out_buf.has_value()) {
-    out = *out_buf;
-    TORCH_CHECK(cl_contig(out) && out.scalar_type() == torch::kBFloat16 &&
-                out.size(0) == b && out.size(2) == oh && out.size(3) == ow &&
-                out_off + kout <= out.size(1),
-                "out buffer must be CL bf16 (B, >=off+kout, OH, OW)");
-    ldc = (int)out.size(1);
-    optr = static_cast<char*>(out.data_ptr()) + out_off * 2;
     // x and out may be ONE buffer (the in-place dense step) when the read
     // and written channel slices are disjoint; any other overlap of the two
     // memories is refused before anything is launched
@@ -741,47 +650,42 @@ torch::Tensor conv2d_nhwc(torch::Tensor x, torch::Tensor w,
                   "conv2d_nhwc: the read and written channel slices of one "
                   "buffer overlap");
     }
-  } else {
-    out = torch::empty({(long)b, oh, ow, kout}, x.options())
-              .permute({0, 3, 1, 2});
-    optr = out.data_ptr();
   }
-  if (inline_pad)
-    vfa_conv2d_nhwc(static_cast<const char*>(xp.data_ptr()) + in_off * 2,
-                    w.data_ptr(), bptr, rptr,
-                    zpage.data_ptr(), optr, b, h, ww, c8, oh, ow,
-                    kout, kh, kw, (int)stride_h, (int)stride_w, (int)pt,
-                    (int)pl, ldc, (int)act, (int)dil_h, (int)dil_w,
-                    slice ? xc : c8, stream);
-  else
-    vfa_conv2d_nhwc(xp.data_ptr(), w.data_ptr(), bptr, rptr,
-                    zpage.data_ptr(), optr, b, hp, wp, c8, oh,
-                    ow, kout, kh, kw, (int)stride_h, (int)stride_w, 0, 0,
-                    ldc, (int)act, (int)dil_h, (int)dil_w, c8, stream);
+  ConvGeom g;
+  g.b = b;
+  g.hp = inline_pad ? h : hp;    // a materialized pad leaves none inline
+  g.wp = inline_pad ? ww : wp;
+  g.cin = c8;
+  g.oh = oh;
+  g.ow = ow;
+  g.kout = kout;
+  g.kh = kh;
+  g.kw = kw;
+  g.sh = (int)stride_h;
+  g.sw = (int)stride_w;
+  g.pt = inline_pad ? (int)pt : 0;
+  g.pl = inline_pad ? (int)pl : 0;
+  g.kr = kh * kw * c8;
+  ConvAddr a;
+  a.dh = (int)dil_h;
+  a.dw = (int)dil_w;
+  a.ldx = slice ? xc : c8;       // a slice is always inline_pad (c % 8 == 0)
+  vfa_conv2d_nhwc(static_cast<const char*>(xp.data_ptr()) + in_off * 2,
+                  w.data_ptr(), bptr, rptr, zpage.data_ptr(), optr, g, a, ldc,
+                  (int)act, stream);
   return out;
 }
 
-// Output side of the transposed convs: a new channels_last (B, K, 2H, 2W)
-// tensor, or the channel slice [out_off, out_off + K) of out_buf, which
-// must not overlap x in memory.  Returns (tensor, first slice element, ldo).
+// Output side of the transposed convs: out_slice for a (B, K, 2H, 2W)
+// result, where out_buf must not overlap x in memory.
 std::tuple<torch::Tensor, void*, int> tconv_out(
-    const torch::Tensor& x, c10::optional<torch::Tensor> out_buf,
+    const torch::Tensor& x, const c10::optional<torch::Tensor>& out_buf,
     int64_t out_off, int kout) {
-  const long b = x.size(0), oh = 2 * x.size(2), ow = 2 * x.size(3);
-  if (!out_buf.has_value()) {
-    TORCH_CHECK(out_off == 0, "out_off needs out");
-    auto out = torch::empty({b, oh, ow, (long)kout}, x.options())
-                   .permute({0, 3, 1, 2});
-    return {out, out.data_ptr(), kout};
-  }
-  auto out = *out_buf;
-  TORCH_CHECK(out.is_cuda() && out.dim() == 4 &&
-              out.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
-              out.scalar_type() == torch::kBFloat16 && out.size(0) == b &&
-              out.size(2) == oh && out.size(3) == ow && out_off >= 0 &&
-              out_off + kout <= out.size(1),
-              "out buffer must be CL bf16 (B, >=off+K_out, 2H, 2W)");
-  if (x.numel() > 0 && out.numel() > 0) {
+  if (!out_buf.has_value()) TORCH_CHECK(out_off == 0, "out_off needs out");
+  auto res = out_slice(out_buf, out_off, x.size(0), kout, 2 * x.size(2),
+                       2 * x.size(3), x.options());
+  const auto& out = std::get<0>(res);
+  if (out_buf.has_value() && x.numel() > 0 && out.numel() > 0) {
     // extent of x through its strides (it may be any strided view)
     long long span = 1;
     for (int d = 0; d < 4; ++d) span += (x.size(d) - 1) * x.stride(d);
@@ -790,8 +694,7 @@ std::tuple<torch::Tensor, void*, int> tconv_out(
     TORCH_CHECK(!(xb < ob + out.numel() * 2 && ob < xb + span * 2),
                 "conv_transpose2d: out must not overlap x in memory");
   }
-  return {out, static_cast<char*>(out.data_ptr()) + out_off * 2,
-          (int)out.size(1)};
+  return res;
 }
 
 // P-form transposed conv (4x4, stride 2, padding 1).  x channels_last bf16;
@@ -821,13 +724,7 @@ torch::Tensor conv_transpose2d_nhwc(torch::Tensor x, torch::Tensor wp,
   TORCH_CHECK(vfa_tconv_lds_bytes(c, kout) <= 64 * 1024,
               "conv_transpose2d_nhwc: C too large for the LDS-resident weight");
   const int b = (int)x.size(0), h = (int)x.size(2), w = (int)x.size(3);
-  const void* bptr = nullptr;
-  torch::Tensor bc;
-  if (bias.has_value()) {
-    bc = bias->contiguous().to(torch::kBFloat16);
-    TORCH_CHECK(bc.numel() == kout);
-    bptr = bc.data_ptr();
-  }
+  auto [bc, bptr] = bf16_bias(bias, kout);
   auto [out, optr, ldo] = tconv_out(x, out_buf, out_off, kout);
   if (x.numel() == 0) return out;
   auto part = torch::empty({(long)b * h * w, 16L * kout},
@@ -853,13 +750,7 @@ torch::Tensor conv_transpose2d_small(torch::Tensor x, torch::Tensor w,
                   w.size(1) <= 2 && w.size(2) == 4 && w.size(3) == 4,
               "weight must be contiguous bf16 (C, K_out <= 2, 4, 4)");
   const int kout = (int)w.size(1);
-  const void* bptr = nullptr;
-  torch::Tensor bc;
-  if (bias.has_value()) {
-    bc = bias->contiguous().to(torch::kBFloat16);
-    TORCH_CHECK(bc.numel() == kout);
-    bptr = bc.data_ptr();
-  }
+  auto [bc, bptr] = bf16_bias(bias, kout);
   auto [out, optr, ldo] = tconv_out(x, out_buf, out_off, kout);
   if (x.numel() == 0) return out;
   vfa_tconv_direct(x.data_ptr(), w.data_ptr(), bptr, optr, (int)x.size(0),
@@ -888,8 +779,7 @@ torch::Tensor temporal_merge(torch::Tensor y, int64_t b, int64_t kt,
   const int h = (int)y.size(2), w = (int)y.size(3);
   const int o = cin / (int)kt, t = bt / (int)b;
   const int to = (int)((t + p0 + p1 - kt) / st + 1);
-  auto out = torch::empty({(long)b * to, h, w, o}, y.options())
-                 .permute({0, 3, 1, 2});
+  auto out = empty_nhwc(b * to, o, h, w, y.options());
   vfa_temporal_merge(y.data_ptr(), out.data_ptr(), (int)b, t, to, (int)kt,
                      (int)st, (int)p0, o, (long long)h * w, relu ? 1 : 0,
                      dtype_tag(y), current_stream());
@@ -906,8 +796,7 @@ torch::Tensor avgpool2d_nhwc(torch::Tensor x, int64_t k) {
   TORCH_CHECK(k >= 1 && k <= x.size(2) && k <= x.size(3),
               "avgpool2d_nhwc: window larger than the input");
   const int64_t oh = x.size(2) / k, ow = x.size(3) / k;
-  auto out = torch::empty({x.size(0), oh, ow, x.size(1)}, x.options())
-                 .permute({0, 3, 1, 2});
+  auto out = empty_nhwc(x.size(0), x.size(1), oh, ow, x.options());
   vfa_avgpool2d_nhwc(x.data_ptr(), out.data_ptr(), x.size(0), (int)x.size(1),
                      (int)x.size(2), (int)x.size(3), (int)oh, (int)ow, (int)k,
                      current_stream());

@@ -39,29 +39,10 @@
 // of its own two runs; profiles/pwc_decoder.md).
 #include "mfma_tile.h"
 
-// the one copy of the tile choice (defined below; also bound to Python as
-// _ext.conv2d_tile so a test can assert which kernel a shape runs)
-extern "C" void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn);
-
 namespace {
 
-struct ConvGeom {
-  int b, hp, wp, cin;       // input dims as addressed (REAL h/w when the
-                            // kernel pads inline; pre-padded dims when the
-                            // pad was materialized, with pt = pl = 0)
-  int oh, ow, kout;         // output
-  int kh, kw, sh, sw;       // filter / stride
-  int pt, pl;               // inline zero-pad (top/left); bottom/right are
-                            // implied by oh/ow + the validity check
-  int kr;                   // KH*KW*C
-};
-
-// tap / pixel addressing beyond the plain conv
-struct ConvAddr {
-  int dh, dw;               // dilation
-  int ldx;                  // input pixel stride in elements (>= cin; cin
-                            // stays the width the K index runs over)
-};
+// ConvGeom / ConvAddr (the geometry the host fills and the kernel takes by
+// value) are declared in vfa_api.h
 
 // decompose output-pixel index m -> (image base, receptive-field origin)
 struct PixRef {
@@ -367,22 +348,10 @@ void vfa_conv2d_pick_tile(int m, int kout, int* bm, int* bn) {
   }
 }
 
-// act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
-// pt/pl: inline zero-pad applied by the kernel (zp = 1 KiB zero page);
-// pass 0 with pre-padded h/w when the pad was materialized
-// ldc: output row stride in elements (= kout normally; larger when the
-// epilogue writes a channel slice of a wider NHWC buffer)
-// dh/dw: dilation.  ldx: input pixel stride in elements (= cin normally;
-// larger when x points at a channel slice of a wider NHWC buffer)
 void vfa_conv2d_nhwc(const void* x, const void* w, const void* bias,
-                     const void* res, const void* zp, void* out, int b,
-                     int hp, int wp, int cin, int oh, int ow, int kout,
-                     int kh, int kw, int sh, int sw, int pt, int pl,
-                     int ldc, int act, int dh, int dw, int ldx,
+                     const void* res, const void* zp, void* out,
+                     const ConvGeom& g, const ConvAddr& a, int ldc, int act,
                      hipStream_t stream) {
-  ConvGeom g{b, hp, wp, cin, oh, ow, kout, kh, kw, sh, sw, pt, pl,
-             kh * kw * cin};
-  const ConvAddr a{dh, dw, ldx};
   dispatch_act(act, [&](auto id) {
     launch_conv<decltype(id)::value>(x, w, bias, res, zp, out, g, a, ldc,
                                      stream);

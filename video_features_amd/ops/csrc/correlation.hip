@@ -227,21 +227,11 @@ void vfa_corr_repack(const void* in, void* out, int b, int c, int h, int w,
   long long total = (long long)b * hp * wp * c;
   int block = 256;
   int grid = (int)min((total + block - 1) / block, (long long)8192);
-  switch (dtype) {
-    case VFA_F32:
-      hipLaunchKernelGGL((repack_kernel<float>), dim3(grid), dim3(block), 0,
-                         stream, (const float*)in, (float*)out, b, c, h, w);
-      break;
-    case VFA_BF16:
-      hipLaunchKernelGGL((repack_kernel<__hip_bfloat16>), dim3(grid),
-                         dim3(block), 0, stream, (const __hip_bfloat16*)in,
-                         (__hip_bfloat16*)out, b, c, h, w);
-      break;
-    case VFA_F16:
-      hipLaunchKernelGGL((repack_kernel<__half>), dim3(grid), dim3(block), 0,
-                         stream, (const __half*)in, (__half*)out, b, c, h, w);
-      break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((repack_kernel<T>), dim3(grid), dim3(block), 0, stream,
+                       (const T*)in, (T*)out, b, c, h, w);
+  });
 }
 
 // f1: NCHW original; f1p/f2p: padded NHWC (from vfa_corr_repack);
@@ -250,18 +240,10 @@ void vfa_corr_repack(const void* in, void* out, int b, int c, int h, int w,
 void vfa_pwc_correlation(const void* f1, const void* f1p, const void* f2p,
                          void* out, int b, int c, int h, int w, int dtype,
                          int ldo, int leaky, hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32:
-      launch_corr<float>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky, stream);
-      break;
-    case VFA_BF16:
-      launch_corr<__hip_bfloat16>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky,
-                                  stream);
-      break;
-    case VFA_F16:
-      launch_corr<__half>(f1, f1p, f2p, out, b, c, h, w, ldo, leaky, stream);
-      break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_corr<typename decltype(t)::type>(f1, f1p, f2p, out, b, c, h, w,
+                                            ldo, leaky, stream);
+  });
 }
 
 // f1, f2: unpadded channels_last bf16 (B, C, H, W), C <= 256; out: the first

@@ -62,20 +62,16 @@ extern "C" {
 
 void vfa_quick_gelu(const void* in, void* out, long long n, int dtype,
                     hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_act<float, 0>(in, out, n, stream); break;
-    case VFA_BF16: launch_act<__hip_bfloat16, 0>(in, out, n, stream); break;
-    case VFA_F16: launch_act<__half, 0>(in, out, n, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_act<typename decltype(t)::type, 0>(in, out, n, stream);
+  });
 }
 
 void vfa_gelu_tanh(const void* in, void* out, long long n, int dtype,
                    hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_act<float, 1>(in, out, n, stream); break;
-    case VFA_BF16: launch_act<__hip_bfloat16, 1>(in, out, n, stream); break;
-    case VFA_F16: launch_act<__half, 1>(in, out, n, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_act<typename decltype(t)::type, 1>(in, out, n, stream);
+  });
 }
 
 }  // extern "C"

@@ -129,17 +129,10 @@ extern "C" {
 void vfa_instance_norm2d(const void* x, void* out, int b, int c, int hw,
                          float eps, int relu, int nhwc, int dtype,
                          hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32:
-      launch_in2d<float>(x, out, b, c, hw, eps, relu, nhwc, stream);
-      break;
-    case VFA_BF16:
-      launch_in2d<__hip_bfloat16>(x, out, b, c, hw, eps, relu, nhwc, stream);
-      break;
-    case VFA_F16:
-      launch_in2d<__half>(x, out, b, c, hw, eps, relu, nhwc, stream);
-      break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_in2d<typename decltype(t)::type>(x, out, b, c, hw, eps, relu, nhwc,
+                                            stream);
+  });
 }
 
 }  // extern "C"

@@ -382,12 +382,9 @@ void launch_ln(const void* in, const void* w, const void* b, void* out,
 extern "C" void vfa_layer_norm(const void* in, const void* w, const void* b,
                                void* out, long long rows, int d, float eps,
                                int dtype, hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_ln<float>(in, w, b, out, rows, d, eps, stream); break;
-    case VFA_BF16:
-      launch_ln<__hip_bfloat16>(in, w, b, out, rows, d, eps, stream); break;
-    case VFA_F16: launch_ln<__half>(in, w, b, out, rows, d, eps, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_ln<typename decltype(t)::type>(in, w, b, out, rows, d, eps, stream);
+  });
 }
 
 // rows = frames * (p + 1); d % 8 == 0 (checked by the binding)
@@ -397,20 +394,10 @@ extern "C" void vfa_clip_embed_ln(const void* pe, const void* cls,
                                   int p, int d, float eps, int dtype,
                                   hipStream_t stream) {
   if (rows <= 0) return;
-  switch (dtype) {
-    case VFA_F32:
-      launch_clip_embed_ln<float>(pe, cls, pos, w, b, out, rows, p, d, eps,
-                                  stream);
-      break;
-    case VFA_BF16:
-      launch_clip_embed_ln<__hip_bfloat16>(pe, cls, pos, w, b, out, rows, p,
-                                           d, eps, stream);
-      break;
-    case VFA_F16:
-      launch_clip_embed_ln<__half>(pe, cls, pos, w, b, out, rows, p, d, eps,
-                                   stream);
-      break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_clip_embed_ln<typename decltype(t)::type>(pe, cls, pos, w, b, out,
+                                                     rows, p, d, eps, stream);
+  });
 }
 
 extern "C" void vfa_layer_norm_residual(const void* x, const void* res,
@@ -418,57 +405,20 @@ extern "C" void vfa_layer_norm_residual(const void* x, const void* res,
                                         void* y, void* s_out, long long rows,
                                         int d, float eps, int dtype,
                                         hipStream_t stream) {
-  if (d <= 4096) {
-    const unsigned grid = (unsigned)((rows + 3) / 4);
-    switch (dtype) {
-      case VFA_F32:
-        hipLaunchKernelGGL((layernorm_res_wave_kernel<float>), dim3(grid),
-                           dim3(256), 0, stream, (const float*)x,
-                           (const float*)res, (const float*)w,
-                           (const float*)b, (float*)y, (float*)s_out, rows,
-                           d, eps);
-        break;
-      case VFA_BF16:
-        hipLaunchKernelGGL((layernorm_res_wave_kernel<__hip_bfloat16>),
-                           dim3(grid), dim3(256), 0, stream,
-                           (const __hip_bfloat16*)x,
-                           (const __hip_bfloat16*)res,
-                           (const __hip_bfloat16*)w, (const __hip_bfloat16*)b,
-                           (__hip_bfloat16*)y, (__hip_bfloat16*)s_out, rows,
-                           d, eps);
-        break;
-      case VFA_F16:
-        hipLaunchKernelGGL((layernorm_res_wave_kernel<__half>), dim3(grid),
-                           dim3(256), 0, stream, (const __half*)x,
-                           (const __half*)res, (const __half*)w,
-                           (const __half*)b, (__half*)y, (__half*)s_out,
-                           rows, d, eps);
-        break;
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (d <= 4096) {
+      const unsigned grid = (unsigned)((rows + 3) / 4);
+      hipLaunchKernelGGL((layernorm_res_wave_kernel<T>), dim3(grid),
+                         dim3(256), 0, stream, (const T*)x, (const T*)res,
+                         (const T*)w, (const T*)b, (T*)y, (T*)s_out, rows, d,
+                         eps);
+      return;
     }
-    return;
-  }
-  int block = d >= 2048 ? 512 : 256;
-  switch (dtype) {
-    case VFA_F32:
-      hipLaunchKernelGGL((layernorm_res_kernel<float>), dim3((unsigned)rows),
-                         dim3(block), 0, stream, (const float*)x,
-                         (const float*)res, (const float*)w, (const float*)b,
-                         (float*)y, (float*)s_out, (int)rows, d, eps);
-      break;
-    case VFA_BF16:
-      hipLaunchKernelGGL((layernorm_res_kernel<__hip_bfloat16>),
-                         dim3((unsigned)rows), dim3(block), 0, stream,
-                         (const __hip_bfloat16*)x, (const __hip_bfloat16*)res,
-                         (const __hip_bfloat16*)w, (const __hip_bfloat16*)b,
-                         (__hip_bfloat16*)y, (__hip_bfloat16*)s_out,
-                         (int)rows, d, eps);
-      break;
-    case VFA_F16:
-      hipLaunchKernelGGL((layernorm_res_kernel<__half>), dim3((unsigned)rows),
-                         dim3(block), 0, stream, (const __half*)x,
-                         (const __half*)res, (const __half*)w,
-                         (const __half*)b, (__half*)y, (__half*)s_out,
-                         (int)rows, d, eps);
-      break;
-  }
+    int block = d >= 2048 ? 512 : 256;
+    hipLaunchKernelGGL((layernorm_res_kernel<T>), dim3((unsigned)rows),
+                       dim3(block), 0, stream, (const T*)x, (const T*)res,
+                       (const T*)w, (const T*)b, (T*)y, (T*)s_out, (int)rows,
+                       d, eps);
+  });
 }

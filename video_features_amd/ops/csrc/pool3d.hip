@@ -152,45 +152,34 @@ void vfa_avgpool2d_nhwc(const void* x, void* out, long long n, int c, int ih,
                      k, 1.f / (float)(k * k));
 }
 
-void vfa_maxpool2d_same(const void* x, void* out, long long n, int c, int ih,
-                        int iw, int oh, int ow, int kh, int kw, int sh,
-                        int sw, int ph, int pw, int nhwc, int dtype,
+void vfa_maxpool2d_same(const void* x, void* out, long long n, int c,
+                        const PoolGeom& g, int nhwc, int dtype,
                         hipStream_t stream) {
-  const long long total = n * (long long)c * oh * ow;
+  const long long total = n * (long long)c * g.out[0] * g.out[1];
   const int grid = (int)min((total + 255) / 256, (long long)65536);
-#define VFA_MP2_CASE(T)                                                       \
-  if (nhwc)                                                                   \
-    hipLaunchKernelGGL((maxpool2d_same_kernel<T, true>), dim3(grid),          \
-                       dim3(256), 0, stream, (const T*)x, (T*)out, n, c, ih,  \
-                       iw, oh, ow, kh, kw, sh, sw, ph, pw);                   \
-  else                                                                        \
-    hipLaunchKernelGGL((maxpool2d_same_kernel<T, false>), dim3(grid),         \
-                       dim3(256), 0, stream, (const T*)x, (T*)out, n, c, ih,  \
-                       iw, oh, ow, kh, kw, sh, sw, ph, pw);
-  switch (dtype) {
-    case VFA_F32: VFA_MP2_CASE(float) break;
-    case VFA_BF16: VFA_MP2_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_MP2_CASE(__half) break;
-  }
-#undef VFA_MP2_CASE
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      hipLaunchKernelGGL((maxpool2d_same_kernel<T, decltype(cl)::value>),
+                         dim3(grid), dim3(256), 0, stream, (const T*)x,
+                         (T*)out, n, c, g.in[0], g.in[1], g.out[0], g.out[1],
+                         g.k[0], g.k[1], g.s[0], g.s[1], g.pad[0], g.pad[1]);
+    });
+  });
 }
 
-void vfa_maxpool3d_same(const void* x, void* out, long long bc, int it,
-                        int ih, int iw, int ot, int oh, int ow, int kt,
-                        int kh, int kw, int st, int sh, int sw, int pt,
-                        int ph, int pw, int dtype, hipStream_t stream) {
-  const long long total = bc * ot * oh * ow;
+void vfa_maxpool3d_same(const void* x, void* out, long long bc,
+                        const PoolGeom& g, int dtype, hipStream_t stream) {
+  const long long total = bc * g.out[0] * g.out[1] * g.out[2];
   const int grid = (int)min((total + 255) / 256, (long long)16384);
-#define VFA_MP_CASE(T)                                                        \
-  hipLaunchKernelGGL((maxpool3d_same_kernel<T>), dim3(grid), dim3(256), 0,    \
-                     stream, (const T*)x, (T*)out, bc, it, ih, iw, ot, oh,    \
-                     ow, kt, kh, kw, st, sh, sw, pt, ph, pw);
-  switch (dtype) {
-    case VFA_F32: VFA_MP_CASE(float) break;
-    case VFA_BF16: VFA_MP_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_MP_CASE(__half) break;
-  }
-#undef VFA_MP_CASE
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((maxpool3d_same_kernel<T>), dim3(grid), dim3(256), 0,
+                       stream, (const T*)x, (T*)out, bc, g.in[0], g.in[1],
+                       g.in[2], g.out[0], g.out[1], g.out[2], g.k[0], g.k[1],
+                       g.k[2], g.s[0], g.s[1], g.s[2], g.pad[0], g.pad[1],
+                       g.pad[2]);
+  });
 }
 
 }  // extern "C"

@@ -271,72 +271,41 @@ __global__ void gru_out_kernel(const T* __restrict__ q,
   }
 }
 
-template <typename T>
-void launch_corr_lookup(const float* l0, const float* l1, const float* l2,
-                        const float* l3, const float* coords, void* out,
-                        int levels, int4 hs, int4 ws, long long npix, int hw,
-                        int lds_floats, int nhwc, hipStream_t stream) {
-  constexpr int PPB = 8;
-  if (lds_floats > 0 && lds_floats * 4 * PPB <= 64 * 1024) {
-    const dim3 grid((unsigned)((npix + PPB - 1) / PPB));
-    const dim3 block(64, PPB);
-    if (nhwc)
-      hipLaunchKernelGGL((corr_lookup_lds_kernel<T, 4, true, PPB>), grid,
-                         block, lds_floats * 4 * PPB, stream, l0, l1, l2, l3,
-                         coords, (T*)out, levels, hs, ws, npix, hw,
-                         lds_floats);
-    else
-      hipLaunchKernelGGL((corr_lookup_lds_kernel<T, 4, false, PPB>), grid,
-                         block, lds_floats * 4 * PPB, stream, l0, l1, l2, l3,
-                         coords, (T*)out, levels, hs, ws, npix, hw,
-                         lds_floats);
-  } else {
-    const long long total = npix * levels * 81;
-    const int grid = (int)min((total + 255) / 256, (long long)16384);
-    if (nhwc)
-      hipLaunchKernelGGL((corr_lookup_gmem_kernel<T, 4, true>), dim3(grid),
-                         dim3(256), 0, stream, l0, l1, l2, l3, coords,
-                         (T*)out, levels, hs, ws, npix, hw);
-    else
-      hipLaunchKernelGGL((corr_lookup_gmem_kernel<T, 4, false>), dim3(grid),
-                         dim3(256), 0, stream, l0, l1, l2, l3, coords,
-                         (T*)out, levels, hs, ws, npix, hw);
-  }
-}
-
 }  // namespace
 
 extern "C" {
 
-void vfa_corr_lookup(const void* l0, const void* l1, const void* l2,
-                     const void* l3, const void* coords, void* out,
-                     int levels, int h0, int w0, int h1, int w1, int h2,
-                     int w2, int h3, int w3, long long npix, int hw,
-                     int lds_floats, int nhwc, int dtype,
-                     hipStream_t stream) {
-  const int4 hs = {h0, h1, h2, h3};
-  const int4 ws = {w0, w1, w2, w3};
-  switch (dtype) {
-    case VFA_F32:
-      launch_corr_lookup<float>((const float*)l0, (const float*)l1,
-                                (const float*)l2, (const float*)l3,
-                                (const float*)coords, out, levels, hs, ws,
-                                npix, hw, lds_floats, nhwc, stream);
-      break;
-    case VFA_BF16:
-      launch_corr_lookup<__hip_bfloat16>((const float*)l0, (const float*)l1,
-                                         (const float*)l2, (const float*)l3,
-                                         (const float*)coords, out, levels,
-                                         hs, ws, npix, hw, lds_floats, nhwc,
-                                         stream);
-      break;
-    case VFA_F16:
-      launch_corr_lookup<__half>((const float*)l0, (const float*)l1,
-                                 (const float*)l2, (const float*)l3,
-                                 (const float*)coords, out, levels, hs, ws,
-                                 npix, hw, lds_floats, nhwc, stream);
-      break;
-  }
+void vfa_corr_lookup(const CorrPyramid& pyr, const void* coords, void* out,
+                     int levels, long long npix, int hw, int lds_floats,
+                     int nhwc, int dtype, hipStream_t stream) {
+  const int4 hs = {pyr.hs[0], pyr.hs[1], pyr.hs[2], pyr.hs[3]};
+  const int4 ws = {pyr.ws[0], pyr.ws[1], pyr.ws[2], pyr.ws[3]};
+  const float* l0 = (const float*)pyr.lvl[0];
+  const float* l1 = (const float*)pyr.lvl[1];
+  const float* l2 = (const float*)pyr.lvl[2];
+  const float* l3 = (const float*)pyr.lvl[3];
+  const float* xy = (const float*)coords;
+  constexpr int PPB = 8;
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      constexpr bool NHWC = decltype(cl)::value;
+      if (lds_floats > 0 && lds_floats * 4 * PPB <= 64 * 1024) {
+        const dim3 grid((unsigned)((npix + PPB - 1) / PPB));
+        const dim3 block(64, PPB);
+        hipLaunchKernelGGL((corr_lookup_lds_kernel<T, 4, NHWC, PPB>), grid,
+                           block, lds_floats * 4 * PPB, stream, l0, l1, l2,
+                           l3, xy, (T*)out, levels, hs, ws, npix, hw,
+                           lds_floats);
+      } else {
+        const long long total = npix * levels * 81;
+        const int grid = (int)min((total + 255) / 256, (long long)16384);
+        hipLaunchKernelGGL((corr_lookup_gmem_kernel<T, 4, NHWC>), dim3(grid),
+                           dim3(256), 0, stream, l0, l1, l2, l3, xy, (T*)out,
+                           levels, hs, ws, npix, hw);
+      }
+    });
+  });
 }
 
 void vfa_convex_upsample(const void* flow, const void* mask, void* out, int b,
@@ -344,21 +313,14 @@ void vfa_convex_upsample(const void* flow, const void* mask, void* out, int b,
                          hipStream_t stream) {
   const long long total = (long long)b * h * w * 64;
   const int grid = (int)min((total + 255) / 256, (long long)16384);
-#define VFA_CU_CASE(T)                                                        \
-  if (nhwc)                                                                   \
-    hipLaunchKernelGGL((convex_upsample_kernel<T, true>), dim3(grid),         \
-                       dim3(256), 0, stream, (const T*)flow, (const T*)mask,  \
-                       (T*)out, b, h, w);                                     \
-  else                                                                        \
-    hipLaunchKernelGGL((convex_upsample_kernel<T, false>), dim3(grid),        \
-                       dim3(256), 0, stream, (const T*)flow, (const T*)mask,  \
-                       (T*)out, b, h, w);
-  switch (dtype) {
-    case VFA_F32: VFA_CU_CASE(float) break;
-    case VFA_BF16: VFA_CU_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_CU_CASE(__half) break;
-  }
-#undef VFA_CU_CASE
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      hipLaunchKernelGGL((convex_upsample_kernel<T, decltype(cl)::value>),
+                         dim3(grid), dim3(256), 0, stream, (const T*)flow,
+                         (const T*)mask, (T*)out, b, h, w);
+    });
+  });
 }
 
 void vfa_gru_zr(const void* zr, const void* hx, void* rhx, void* z, int b,
@@ -366,42 +328,29 @@ void vfa_gru_zr(const void* zr, const void* hx, void* rhx, void* z, int b,
                 hipStream_t stream) {
   const long long total = (long long)b * c * hw;
   const int grid = (int)min((total + 255) / 256, (long long)16384);
-#define VFA_ZR_CASE(T)                                                        \
-  if (nhwc)                                                                   \
-    hipLaunchKernelGGL((gru_zr_kernel<T, true>), dim3(grid), dim3(256), 0,    \
-                       stream, (const T*)zr, (const T*)hx, (T*)rhx, (T*)z, b, \
-                       c, cx, hw);                                            \
-  else                                                                        \
-    hipLaunchKernelGGL((gru_zr_kernel<T, false>), dim3(grid), dim3(256), 0,   \
-                       stream, (const T*)zr, (const T*)hx, (T*)rhx, (T*)z, b, \
-                       c, cx, hw);
-  switch (dtype) {
-    case VFA_F32: VFA_ZR_CASE(float) break;
-    case VFA_BF16: VFA_ZR_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_ZR_CASE(__half) break;
-  }
-#undef VFA_ZR_CASE
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      hipLaunchKernelGGL((gru_zr_kernel<T, decltype(cl)::value>), dim3(grid),
+                         dim3(256), 0, stream, (const T*)zr, (const T*)hx,
+                         (T*)rhx, (T*)z, b, c, cx, hw);
+    });
+  });
 }
 
 void vfa_gru_out(const void* q, const void* z, void* hx, int b, int c, int cx,
                  long long hw, int nhwc, int dtype, hipStream_t stream) {
   const long long total = (long long)b * c * hw;
   const int grid = (int)min((total + 255) / 256, (long long)16384);
-#define VFA_GO_CASE(T)                                                        \
-  if (nhwc)                                                                   \
-    hipLaunchKernelGGL((gru_out_kernel<T, true>), dim3(grid), dim3(256), 0,   \
-                       stream, (const T*)q, (const T*)z, (T*)hx, b, c, cx,    \
-                       hw);                                                   \
-  else                                                                        \
-    hipLaunchKernelGGL((gru_out_kernel<T, false>), dim3(grid), dim3(256), 0,  \
-                       stream, (const T*)q, (const T*)z, (T*)hx, b, c, cx,    \
-                       hw);
-  switch (dtype) {
-    case VFA_F32: VFA_GO_CASE(float) break;
-    case VFA_BF16: VFA_GO_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_GO_CASE(__half) break;
-  }
-#undef VFA_GO_CASE
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      hipLaunchKernelGGL((gru_out_kernel<T, decltype(cl)::value>), dim3(grid),
+                         dim3(256), 0, stream, (const T*)q, (const T*)z,
+                         (T*)hx, b, c, cx, hw);
+    });
+  });
 }
 
 }  // extern "C"
+

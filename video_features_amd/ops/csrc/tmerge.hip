@@ -44,21 +44,14 @@ void vfa_temporal_merge(const void* y, void* out, int b, int t, int to,
                         int relu, int dtype, hipStream_t stream) {
   const long long total = (long long)b * to * hw * o;
   const int grid = (int)min((total + 255) / 256, (long long)65536);
-#define VFA_TM_CASE(T)                                                        \
-  if (relu)                                                                   \
-    hipLaunchKernelGGL((temporal_merge_kernel<T, true>), dim3(grid),          \
-                       dim3(256), 0, stream, (const T*)y, (T*)out, b, t, to,  \
-                       kt, st, p0, o, hw);                                    \
-  else                                                                        \
-    hipLaunchKernelGGL((temporal_merge_kernel<T, false>), dim3(grid),         \
-                       dim3(256), 0, stream, (const T*)y, (T*)out, b, t, to,  \
-                       kt, st, p0, o, hw);
-  switch (dtype) {
-    case VFA_F32: VFA_TM_CASE(float) break;
-    case VFA_BF16: VFA_TM_CASE(__hip_bfloat16) break;
-    case VFA_F16: VFA_TM_CASE(__half) break;
-  }
-#undef VFA_TM_CASE
+  dispatch_dtype(dtype, [&](auto tt) {
+    using T = typename decltype(tt)::type;
+    dispatch_bool(relu, [&](auto r) {
+      hipLaunchKernelGGL((temporal_merge_kernel<T, decltype(r)::value>),
+                         dim3(grid), dim3(256), 0, stream, (const T*)y,
+                         (T*)out, b, t, to, kt, st, p0, o, hw);
+    });
+  });
 }
 
 }  // extern "C"

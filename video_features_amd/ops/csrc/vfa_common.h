@@ -4,6 +4,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <cstdint>
+#include <type_traits>
+#include "vfa_api.h"
 
 #define VFA_WAVE 64  // CDNA4 wavefront width (not 32)
 
@@ -19,6 +21,29 @@
 
 // dtype tags used across the C-linkage launcher ABI
 enum VfaDType : int { VFA_F32 = 0, VFA_BF16 = 1, VFA_F16 = 2 };
+
+// runtime dtype tag -> compile-time type: calls f(type_tag<T>) with T =
+// float / __hip_bfloat16 / __half, read back in the lambda as
+// `using T = typename decltype(t)::type`; any other tag is a no-op (the
+// bindings reject it, as for dispatch_act).
+template <typename T>
+struct type_tag { using type = T; };
+
+template <typename F>
+inline void dispatch_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case VFA_F32: f(type_tag<float>{}); break;
+    case VFA_BF16: f(type_tag<__hip_bfloat16>{}); break;
+    case VFA_F16: f(type_tag<__half>{}); break;
+    default: break;
+  }
+}
+
+// runtime flag -> compile-time bool: f(std::true_type) or f(std::false_type)
+template <typename F>
+inline void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{}); else f(std::false_type{});
+}
 
 template <typename T>
 __device__ __forceinline__ float to_f32(T v);

@@ -161,12 +161,9 @@ extern "C" {
 
 void vfa_bilinear_warp(const void* x, const void* flow, void* out, int b,
                        int c, int h, int w, int dtype, hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_warp<float>(x, flow, out, b, c, h, w, stream); break;
-    case VFA_BF16:
-      launch_warp<__hip_bfloat16>(x, flow, out, b, c, h, w, stream); break;
-    case VFA_F16: launch_warp<__half>(x, flow, out, b, c, h, w, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_warp<typename decltype(t)::type>(x, flow, out, b, c, h, w, stream);
+  });
 }
 
 // x, out: channels_last bf16 (b, c, h, w) with c % 8 == 0; flow: bf16,
@@ -187,13 +184,10 @@ void vfa_bilinear_warp_nhwc(const void* x, const void* flow, void* out, int b,
 void vfa_grid_sample(const void* x, const void* coords, void* out,
                      long long n, int c, int h, int w, int ho, int wo,
                      int dtype, hipStream_t stream) {
-  switch (dtype) {
-    case VFA_F32: launch_gs<float>(x, coords, out, n, c, h, w, ho, wo, stream); break;
-    case VFA_BF16:
-      launch_gs<__hip_bfloat16>(x, coords, out, n, c, h, w, ho, wo, stream); break;
-    case VFA_F16:
-      launch_gs<__half>(x, coords, out, n, c, h, w, ho, wo, stream); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_gs<typename decltype(t)::type>(x, coords, out, n, c, h, w, ho, wo,
+                                          stream);
+  });
 }
 
 }  // extern "C"
