@@ -169,14 +169,11 @@ class VisionTransformer(nn.Module):
         self.proj = nn.Parameter(scale * torch.randn(w, cfg.output_dim))
 
     def _patch_embed(self, x: torch.Tensor) -> torch.Tensor:
-        """Patch embedding.  Stride==kernel conv IS a reshape + GEMM; on GPU
-        route it to rocBLAS directly instead of an im2col conv."""
+        """Patch embedding.  Stride==kernel conv IS a patch gather + GEMM; on
+        GPU the gather is one ``ops.patchify`` pass and the GEMM goes to
+        hipBLASLt directly instead of an im2col conv."""
         if x.is_cuda:
-            t = x.shape[0]
-            p = self.cfg.patch_size
-            g = x.shape[-1] // p
-            xp = x.reshape(t, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5)
-            xp = xp.reshape(t, g * g, 3 * p * p)
+            xp = ops.patchify(x, self.cfg.patch_size)   # (T, P, 3*p*p)
             w = self.conv1.weight.reshape(self.cfg.width, -1)
             return xp @ w.t()                           # (T, P, W)
         x = self.conv1(x)                               # (T, W, R/p, R/p)

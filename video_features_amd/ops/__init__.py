@@ -200,14 +200,50 @@ def preprocess_u8_chw(frames_u8: torch.Tensor, mean, std,
     return x.to(torch.bfloat16) if bf16 else x
 
 
+def patchify(x: torch.Tensor, p: int) -> torch.Tensor:
+    """(T, C, H, W) → (T, (H/p)·(W/p), C·p·p): the rows a stride == kernel
+    conv reads, patch order (gy, gx), K order (c, py, px) — the layout of
+    ``conv.weight.reshape(out, -1)``.  Pure data movement, bit-identical on
+    every path.
+
+    HIP path (itemsize 2 or 4, p·itemsize % 16 == 0, H % p == W % p == 0,
+    16-B aligned storage): one pass of 16-B vectors, writes coalesced.
+    Everything else — CPU tensors, other shapes, ``VFA_FORCE_TORCH_OPS=1`` —
+    takes the reshape / permute composition."""
+    t, c, h, w = x.shape
+    if h % p or w % p:
+        raise ValueError(f'patchify: H, W = {h}, {w} must be multiples of '
+                         f'p = {p}')
+    es = x.element_size()
+    if (_use_hip(x) and es in (2, 4) and (p * es) % 16 == 0
+            and x.numel() > 0):
+        xc = x.contiguous()
+        if xc.data_ptr() % 16 == 0:
+            return _ext.patchify(xc, int(p))
+    gy, gx = h // p, w // p
+    xp = x.reshape(t, c, gy, p, gx, p).permute(0, 2, 4, 1, 3, 5)
+    return xp.reshape(t, gy * gx, c * p * p)
+
+
+# kernels ops.mhsa_fused can run on the HIP path: 0 is the routing every
+# caller gets (N <= 64: the register-resident kernel; longer: the general
+# flash kernel), 1 the general kernel at any N (its single-tile branch for
+# N <= 64)
+MHSA_VARIANTS = (0, 1)
+
+
 def mhsa_fused(qkv: torch.Tensor, heads: int,
-               scale: Optional[float] = None) -> torch.Tensor:
+               scale: Optional[float] = None, variant: int = 0) -> torch.Tensor:
     """Fused MHSA from the packed qkv projection: (B, N, 3*E) → (B, N, E).
 
     HIP path (bf16, head_dim 64): the MFMA flash kernel consumes the packed
-    layout directly — no permute/contiguous copies on either side.  Torch
-    path: explicit reshape + softmax reference.
+    layout directly — no permute/contiguous copies on either side.
+    ``variant`` picks the kernel per call (``MHSA_VARIANTS``; tests and A/B
+    replays run several in one process) and means nothing on the torch path:
+    explicit reshape + softmax reference.
     """
+    if variant not in MHSA_VARIANTS:
+        raise ValueError(f'mhsa_fused: variant must be one of {MHSA_VARIANTS}')
     b, n, three_e = qkv.shape
     e = three_e // 3
     d = e // heads
@@ -215,7 +251,7 @@ def mhsa_fused(qkv: torch.Tensor, heads: int,
         scale = 1.0 / math.sqrt(d)
     if _use_hip(qkv) and qkv.dtype == torch.bfloat16 and d == 64:
         qkv5 = qkv.view(b, n, 3, heads, d)
-        return _ext.flash_qkv(qkv5.contiguous(), float(scale))
+        return _ext.flash_qkv(qkv5.contiguous(), float(scale), int(variant))
     q, k, v = qkv.view(b, n, 3, heads, d).permute(2, 0, 3, 1, 4).unbind(0)
     o = attention(q.contiguous(), k.contiguous(), v.contiguous(), scale)
     return o.permute(0, 2, 1, 3).reshape(b, n, e)

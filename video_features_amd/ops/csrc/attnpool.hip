@@ -13,12 +13,15 @@
 // projection of token 0 only; kv (B, L, 2C) is packed [k | v] exactly as
 // one GEMM with the concatenated [k_proj; v_proj] weight writes it.
 //   o[b, h] = softmax_j(q_h . k_jh / sqrt(d)) . v_jh,   d = 64
-// One wave per (b, h).  Scores: lane <-> key, each lane reads its key's
-// 128-B head slice as 8 x 16-B loads.  Max / sum cross the wave with
-// shuffles.  PV: lane <-> output dim, keys looped, so each key's V slice is
-// one coalesced 128-B read.  All arithmetic in f32, softmax max-subtracted;
+// One wave per (b, h); 8 lanes share a key, each with one 16-B segment of
+// its 128-B head slice, so every K and V load is 16 B and a wave instruction
+// covers 8 whole keys.  Scores: 8-element partial dots summed over the 8
+// segment lanes.  PV: each lane accumulates its 8 output dims over its key
+// group's keys; the 8 groups are summed once at the end and lanes 0-7 write
+// 16 B each.  All arithmetic in f32, softmax max-subtracted, one rounding;
 // keys are consumed in 64-key chunks with an online rescale, so any L >= 1
-// works (the towers use 50, 82, 145).
+// works (the towers use 50, 82, 145).  L == 1 returns V's values exactly
+// (p = 1, denom = 1, the other groups add zeros).
 #include "vfa_common.h"
 
 namespace {
@@ -56,62 +59,92 @@ __global__ void attnpool_tokens_kernel(const uint4* __restrict__ x,
 }
 
 // 4 waves per block, one (b, h) pair per wave; no LDS, no barrier (waves
-// past the last pair simply exit).
+// past the last pair simply exit).  Lane = (key group g = lane >> 3, 16-B
+// segment sg = lane & 7): round r of a 64-key chunk reads keys c0 + 8r + g,
+// 8 keys x 128 B per wave instruction, and all 8 rounds of K and of V are
+// issued before the first use.
 __global__ __launch_bounds__(256) void attention_pool_d64_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ kv,
     __hip_bfloat16* __restrict__ out, long long bh, int heads, int l,
     float scale) {
   const int lane = threadIdx.x & 63;
+  const int g = lane >> 3, sg = lane & 7;
   const long long pair = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pair >= bh) return;
   const long long bi = pair / heads;
   const int h = (int)(pair % heads);
   const long long c = (long long)heads * 64;
-  // every lane holds the whole (pre-scaled) query head: same address across
-  // the wave, served as a broadcast
-  float qf[64];
-  {
-    const uint4* qp = reinterpret_cast<const uint4*>(q + bi * c + h * 64);
+  // this lane's 8 dims of the (pre-scaled) query head
+  float qf[8];
+  bf16x8_to_f32(
+      *reinterpret_cast<const uint4*>(q + bi * c + h * 64 + sg * 8), qf);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      bf16x8_to_f32(qp[s], qf + 8 * s);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) qf[8 * s + e] *= scale;
-    }
-  }
-  const __hip_bfloat16* kb = kv + bi * l * 2 * c + h * 64;   // k of key 0
-  const __hip_bfloat16* vb = kb + c;                         // v of key 0
-  float m = -INFINITY, denom = 0.f, acc = 0.f;
+  for (int e = 0; e < 8; ++e) qf[e] *= scale;
+  // k of key 0, this lane's segment; v sits c elements further
+  const __hip_bfloat16* kb = kv + bi * l * 2 * c + h * 64 + sg * 8;
+  float m = -INFINITY, denom = 0.f;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int c0 = 0; c0 < l; c0 += 64) {
-    const int nk = min(64, l - c0);          // wave-uniform, >= 1
-    const int j = c0 + lane;
-    float s = -INFINITY;
-    if (j < l) {
-      const uint4* kp =
-          reinterpret_cast<const uint4*>(kb + (long long)j * 2 * c);
+    uint4 kr[8], vr[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int j = c0 + 8 * r + g;
+      kr[r] = vr[r] = uint4{0u, 0u, 0u, 0u};
+      if (j < l) {
+        const __hip_bfloat16* kp = kb + (long long)j * 2 * c;
+        kr[r] = *reinterpret_cast<const uint4*>(kp);
+        vr[r] = *reinterpret_cast<const uint4*>(kp + c);
+      }
+    }
+    // scores: 8-element partial dot, summed over the 8 segment lanes
+    float s[8];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      float kf[8];
+      bf16x8_to_f32(kr[r], kf);
       float dot = 0.f;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        float kf[8];
-        bf16x8_to_f32(kp[u], kf);
+      for (int e = 0; e < 8; ++e) dot += qf[e] * kf[e];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) dot += qf[8 * u + e] * kf[e];
-      }
-      s = dot;
+      for (int off = 1; off < 8; off <<= 1) dot += __shfl_xor(dot, off, 64);
+      s[r] = (c0 + 8 * r + g < l) ? dot : -INFINITY;
+      mx = fmaxf(mx, s[r]);
     }
-    const float m_new = fmaxf(m, wave_allreduce_max(s));   // finite: nk >= 1
-    const float p = (j < l) ? __expf(s - m_new) : 0.f;
-    const float alpha = __expf(m - m_new);                 // 0 on chunk 0
-    denom = denom * alpha + wave_allreduce_sum(p);
-    acc *= alpha;
-    const __hip_bfloat16* vp = vb + (long long)c0 * 2 * c + lane;
-    for (int jj = 0; jj < nk; ++jj) {
-      const float pj = __shfl(p, jj, 64);
-      acc += pj * __bfloat162float(vp[(long long)jj * 2 * c]);
+    // max and sum over the key groups (the 8 lanes of a group agree)
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1)
+      mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    const float m_new = fmaxf(m, mx);      // finite: key c0 is valid
+    const float alpha = __expf(m - m_new); // 0 on chunk 0
+    float psum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] *= alpha;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const float p = __expf(s[r] - m_new);            // 0 for a padded key
+      psum += p;
+      float vf[8];
+      bf16x8_to_f32(vr[r], vf);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += p * vf[e];
     }
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) psum += __shfl_xor(psum, off, 64);
+    denom = denom * alpha + psum;
     m = m_new;
   }
-  out[bi * c + h * 64 + lane] = __float2bfloat16(acc / denom);
+  // sum the key groups' partial outputs; lanes 0-7 hold segment sg
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1)
+      acc[e] += __shfl_xor(acc[e], off, 64);
+    acc[e] /= denom;
+  }
+  if (g == 0)
+    *reinterpret_cast<uint4*>(out + bi * c + h * 64 + sg * 8) =
+        f32_to_bf16x8(acc);
 }
 
 }  // namespace

@@ -295,7 +295,27 @@ torch::Tensor u8_chw_norm(torch::Tensor frames, std::vector<double> mean,
   return out;
 }
 
-torch::Tensor flash_qkv(torch::Tensor qkv, double scale) {
+// (T, C, H, W) -> (T, (H/p)*(W/p), C*p*p); see patchify_kernel
+torch::Tensor patchify(torch::Tensor x, int64_t p) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4,
+              "patchify: contiguous (T, C, H, W) expected");
+  const int64_t es = x.element_size();
+  const int64_t t = x.size(0), c = x.size(1), h = x.size(2), w = x.size(3);
+  TORCH_CHECK((es == 2 || es == 4) && p > 0 && (p * es) % 16 == 0 &&
+              h % p == 0 && w % p == 0,
+              "patchify: itemsize 2 or 4, p * itemsize % 16 == 0 and "
+              "H, W multiples of p required");
+  TORCH_CHECK(c * h * w * es / 16 < (1LL << 31), "patchify: frame too large");
+  auto out = torch::empty({t, (h / p) * (w / p), c * p * p}, x.options());
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+              (uintptr_t)out.data_ptr() % 16 == 0,
+              "patchify: 16-B aligned tensors required");
+  vfa_patchify(x.data_ptr(), out.data_ptr(), t, (int)c, (int)h, (int)w,
+               (int)p, (int)es, current_stream());
+  return out;
+}
+
+torch::Tensor flash_qkv(torch::Tensor qkv, double scale, int64_t variant) {
   // qkv: (B, N, 3, H, D) bf16 contiguous, D == 64 -> out (B, N, H*D)
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 5);
   TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == 64,
@@ -304,8 +324,10 @@ torch::Tensor flash_qkv(torch::Tensor qkv, double scale) {
   const int b = (int)qkv.size(0), n = (int)qkv.size(1);
   const int h = (int)qkv.size(3);
   auto out = torch::empty({b, n, h * 64L}, qkv.options());
+  TORCH_CHECK(variant == 0 || variant == 1, "flash_qkv: variant 0 or 1");
+  TORCH_CHECK((int64_t)b * h * 2 < (1LL << 31), "flash_qkv: too many pairs");
   vfa_flash_qkv(qkv.data_ptr(), out.data_ptr(), b, n, h, (float)scale,
-                current_stream());
+                (int)variant, current_stream());
   return out;
 }
 
@@ -847,11 +869,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grid_sample_bilinear", &grid_sample_bilinear);
   m.def("pwc_correlation", &pwc_correlation);
   m.def("mhsa", &mhsa);
-  m.def("flash_qkv", &flash_qkv);
+  m.def("flash_qkv", &flash_qkv, py::arg("qkv"), py::arg("scale"),
+        py::arg("variant") = 0);
   m.def("mfma_gemm16", &mfma_gemm16);
   m.def("layer_norm_residual", &layer_norm_residual);
   m.def("clip_embed_ln", &clip_embed_ln);
   m.def("u8_chw_norm", &u8_chw_norm);
+  m.def("patchify", &patchify);
   m.def("corr_lookup", &corr_lookup);
   m.def("convex_upsample", &convex_upsample);
   m.def("gru_zr", &gru_zr);

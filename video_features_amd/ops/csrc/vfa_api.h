@@ -124,9 +124,11 @@ void vfa_mhsa_small(const void* q, const void* k, const void* v, void* out,
                     hipStream_t stream);
 
 // --------------------------------------------------- attention_flash.hip
-// qkv (b, n, 3, h, 64) bf16 -> out (b, n, h*64)
+// qkv (b, n, 3, h, 64) bf16 -> out (b, n, h*64).  variant 0: the kernel the
+// shape is routed to (n <= 64: flash_qkv_regs_kernel); 1: the general
+// flash_qkv_kernel at any n
 void vfa_flash_qkv(const void* qkv, void* out, int b, int n, int h,
-                   float scale, hipStream_t stream);
+                   float scale, int variant, hipStream_t stream);
 // d (16, 16) = a (16, 32) @ b (32, 16), f32 in and out: the MFMA self-test
 void vfa_mfma_gemm16(const void* a, const void* b, void* d,
                      hipStream_t stream);
@@ -137,6 +139,11 @@ void vfa_mfma_gemm16(const void* a, const void* b, void* d,
 void vfa_u8_chw_norm(const void* in, void* out, long long t, int h, int w,
                      const float* mean, const float* std, int dtype,
                      hipStream_t stream);
+// in (t, c, h, w) -> out (t, (h/p)*(w/p), c*p*p), K order (c, py, px);
+// itemsize 2 or 4, p*itemsize % 16 == 0, h % p == w % p == 0, 16-B aligned
+// pointers, c*h*w*itemsize/16 < 2^31
+void vfa_patchify(const void* in, void* out, long long t, int c, int h, int w,
+                  int p, int itemsize, hipStream_t stream);
 
 // -------------------------------------------------------------- raft.hip
 // coords (B, 2, H, W) f32 pixel units at level 0, hw = H*W, npix = B*hw;
