@@ -136,7 +136,7 @@ def test_conv2d_act_out_buffer_slice():
 
 def test_conv2d_mod_padded_weight_cache_invalidates():
     """The cached channel-padded weight must refresh when new weights are
-    loaded into the module (version-keyed like cached_cl_weight)."""
+    loaded into the module (version-keyed by ops.derived)."""
     from video_features_amd.ops import conv2d_mod
     torch.manual_seed(0)
     conv = torch.nn.Conv2d(3, 16, 3, 1, 1)

@@ -44,7 +44,7 @@ def child(args) -> int:
     fold_batchnorms(model)
     model = model.to(dev, torch.bfloat16)
     res = model.input_resolution
-    path = 'eager' if ops._env_flag('VFA_NO_CLIPRN') else 'fused'
+    path = 'eager' if ops.env_flag('VFA_NO_CLIPRN') else 'fused'
     try:
         x = torch.randn(args.batch, 3, res, res, device=dev) \
             .to(torch.bfloat16)

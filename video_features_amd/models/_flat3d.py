@@ -11,33 +11,87 @@ backbones run on (B*T, C, H, W) channels_last tensors:
 * a separable pooling window splits exactly into a spatial 2D pool and
   :func:`temporal_max` (max over a separable window commutes).
 
-All helpers keep channels_last layout and support any (kt, stride, pad).
+All helpers keep channels_last layout and support any (kt, stride, pad);
+:func:`conv3d_flat` is the one place the decomposition is written out.
 """
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
+from torch import nn
 
 from .. import ops
 
 
-def cached_cl_weight(mod, name: str, src: torch.Tensor, build):
-    """Per-module cache of transformed conv weights for the flat path.
+def conv3d_flat(conv: nn.Conv3d, xf: torch.Tensor, b: int, *, pads=None,
+                act: str = 'none', pad_channels: bool = None) -> torch.Tensor:
+    """``conv`` on the (B*T, C, H, W) channels_last view ``xf`` of a
+    (B, C, T, H, W) clip → the flattened (B*T', O, H', W') output.
 
-    The flat decomposition slices/permutes the stored Conv3d weights; the
-    resulting views are NOT channels_last-contiguous, and F.conv2d with a
-    non-CL weight silently drops MIOpen's NHWC igemm path (measured: I3D at
-    17 TF/s effective vs RAFT's 911 with module convs).  Build once, store
-    CL-contiguous, invalidate on weight version/dtype/device change."""
-    key = (src._version, src.dtype, src.device, src.data_ptr())
-    cache = mod.__dict__.setdefault('_flat_w_cache', {})
-    ent = cache.get(name)
-    if ent is None or ent[0] != key:
-        val = build()
-        if isinstance(val, torch.Tensor) and val.dim() == 4:
-            val = val.contiguous(memory_format=torch.channels_last)
-        cache[name] = (key, val)
-        return val
-    return ent[1]
+    ``pads``: zero padding ((t0, t1), (h0, h1), (w0, w1)), default the
+    conv's own symmetric padding (TF-SAME callers pass asymmetric ones).
+    ``act``: 'none' or 'relu', fused into the last kernel.
+
+    kt == 1: every st-th frame, then ONE ``ops.conv2d_act`` (which sends an
+    unpadded stride-1 1x1 to the fused MFMA GEMM).  kt > 1: one merged
+    conv2d with kt*O outputs (tap-major) and :func:`temporal_merge`; the
+    bias rides tap kt // 2, which therefore must be valid at every output
+    position (ValueError otherwise).
+
+    The derived weight is cached on ``conv`` (``ops.derived``) and stored
+    channels_last: the sliced / permuted views are not, and a non-CL weight
+    silently drops the NHWC conv paths.  When ``xf`` takes the in-tree path
+    (``ops.native_ready``; ``pad_channels`` overrides) its input channels
+    are zero-padded to a multiple of 8 and the conv kernel's pad pass widens
+    the input to match — stems (C = 3, 2) and the R(2+1)D mid-planes
+    (45, 144, 230, 460, 921) stay off MIOpen."""
+    if act not in ('none', 'relu'):
+        raise ValueError(f'conv3d_flat: unsupported act {act!r}')
+    kt, kh, kw = conv.kernel_size
+    st, sh, sw = conv.stride
+    (t0, t1), (h0, h1), (w0, w1) = pads or [(p, p) for p in conv.padding]
+    o, c = conv.weight.shape[:2]
+    t = xf.shape[0] // b
+    to = (t + t0 + t1 - kt) // st + 1
+    tap = kt // 2
+    if tap < t0 or (to - 1) * st - t0 + tap >= t:
+        raise ValueError(
+            f'conv3d_flat: tap {tap} of kernel {kt}, stride {st}, temporal '
+            f'pad {(t0, t1)} reads padding at T={t}: it carries the bias '
+            'and must be valid at every output position')
+    if pad_channels is None:
+        pad_channels = ops.native_ready(xf)
+    c8 = (c + 7) // 8 * 8 if pad_channels else c
+
+    def make():
+        w = conv.weight.permute(2, 0, 1, 3, 4).reshape(kt * o, c, kh, kw)
+        if c8 > c:
+            w = F.pad(w, (0, 0, 0, 0, 0, c8 - c))
+        w = w.contiguous(memory_format=torch.channels_last)
+        if conv.bias is None or kt == 1:
+            return w, conv.bias
+        bcat = conv.bias.new_zeros(kt * o)
+        bcat[tap * o:(tap + 1) * o] = conv.bias
+        return w, bcat
+
+    w, bias = ops.derived(conv, '_vfa_flat', (conv.weight, conv.bias), make,
+                          c8)
+    pad2 = (h0, h1, w0, w1)
+    if kt == 1:
+        return ops.conv2d_act(temporal_select(xf, b, st), w, bias, (sh, sw),
+                              pad2, act)
+    y = ops.conv2d_act(xf, w, bias, (sh, sw), pad2)
+    return temporal_merge(y, b, kt=kt, st=st, p0=t0, bias_tap=tap,
+                          relu=act == 'relu', p1=t1)
+
+
+def flat_bn_act(x: torch.Tensor, bn, relu: bool) -> torch.Tensor:
+    """BatchNorm3d (== BatchNorm2d per channel on the flattened view; the
+    identity once folded away) and the optional in-place ReLU."""
+    if isinstance(bn, nn.BatchNorm3d):
+        x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight,
+                         bn.bias, bn.training, bn.momentum, bn.eps)
+    return F.relu(x, inplace=True) if relu else x
 
 
 def flatten_time(x: torch.Tensor) -> torch.Tensor:

@@ -35,9 +35,8 @@ from .. import ops
 def _fused_ready(mod: nn.Module, x: torch.Tensor) -> bool:
     # inference path: BNs folded into the convs, bf16 on the GPU with the
     # HIP extension present
-    return (isinstance(mod.bn1, nn.Identity) and x.is_cuda
-            and x.dtype == torch.bfloat16 and ops.hip_available()
-            and not ops._env_flag('VFA_NO_CLIPRN'))
+    return (isinstance(mod.bn1, nn.Identity)
+            and ops.native_ready(x, knob='VFA_NO_CLIPRN'))
 
 
 class Bottleneck(nn.Module):
@@ -113,15 +112,9 @@ class AttentionPool2d(nn.Module):
         ``load_state_dict`` invalidates it."""
         ps = (self.k_proj.weight, self.v_proj.weight,
               self.k_proj.bias, self.v_proj.bias)
-        key = tuple((p._version, p.dtype, p.device, p.data_ptr())
-                    for p in ps)
-        ent = getattr(self, '_vfa_wkv', None)
-        if ent is None or ent[0] != key:
-            with torch.no_grad():
-                self._vfa_wkv = ent = (key,
-                                       torch.cat([ps[0], ps[1]]).contiguous(),
-                                       torch.cat([ps[2], ps[3]]).contiguous())
-        return ent[1], ent[2]
+        return ops.derived(self, '_vfa_wkv', ps, lambda: (
+            torch.cat([ps[0], ps[1]]).contiguous(),
+            torch.cat([ps[2], ps[3]]).contiguous()))
 
     def _forward_fused(self, x):
         """``x``: (B, C, H, W) channels_last bf16 on the GPU."""

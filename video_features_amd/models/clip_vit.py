@@ -117,12 +117,8 @@ class ResidualAttentionBlock(nn.Module):
         (``.to()``: ``data_ptr`` / dtype / device)."""
         src = (self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.ln_2.weight,
                self.ln_2.bias)
-        key = tuple((p._version, p.data_ptr(), p.dtype, p.device)
-                    for p in src)
-        if self._fold is None or self._fold[0] != key:
-            with torch.no_grad():
-                self._fold = (key, ops.fold_ln_linear(*src))
-        return self._fold[1]
+        return ops.derived(self, '_fold', src,
+                           lambda: ops.fold_ln_linear(*src))
 
     def fold_routed(self, x: torch.Tensor) -> bool:
         """Whether ``attn_mlp_folded`` replaces the ``ln_2`` pass for a
@@ -130,7 +126,7 @@ class ResidualAttentionBlock(nn.Module):
         same arithmetic as the pass), on the GPU when both GEMMs run their
         fused kernel — all full 256-row tiles, so not ViT-B/16's 197 tokens
         at most batch sizes."""
-        if ops._env_flag('VFA_NO_LNFOLD'):
+        if ops.env_flag('VFA_NO_LNFOLD'):
             return False
         return not x.is_cuda or (
             ops.fused_ln_tiles(x, self.attn.proj.weight)
@@ -186,7 +182,7 @@ class VisionTransformer(nn.Module):
         x = ops.clip_embed_ln(x, self.class_embedding,
                               self.positional_embedding, self.ln_pre.weight,
                               self.ln_pre.bias, self.ln_pre.eps)
-        full_tail = ops._env_flag('VFA_CLIP_FULL_TAIL')
+        full_tail = ops.env_flag('VFA_CLIP_FULL_TAIL')
         # residual stream carried as (delta, res): every add is fused into
         # the next LayerNorm (ops.layer_norm_residual)
         delta, res = None, x

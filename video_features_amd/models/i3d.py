@@ -46,13 +46,8 @@ def _triple(v) -> Tuple[int, int, int]:
 # ----------------------------------------------------- flattened-time path
 # See models/_flat3d.py: the backbone below the stem runs on (B*T, C, H, W)
 # channels_last tensors (no conv3d, no Im3d2Col).
-from ._flat3d import (flatten_time, unflatten_time, temporal_merge,
-                      temporal_max, cached_cl_weight)
-
-
-def temporal_merge3(y: torch.Tensor, b: int) -> torch.Tensor:
-    """3-tap stride-1 merge (3x3x3 conv, TF-SAME temporal pad (1,1))."""
-    return temporal_merge(y, b, kt=3, st=1, p0=1, bias_tap=1)
+from ._flat3d import (flatten_time, unflatten_time, temporal_max,
+                      conv3d_flat, flat_bn_act)
 
 
 class Unit3D(nn.Module):
@@ -91,57 +86,19 @@ class Unit3D(nn.Module):
 
     def forward_flat(self, xf: torch.Tensor, b: int) -> torch.Tensor:
         """Flattened-time forward on (B*T, C, H, W) channels_last (see the
-        module comment): 1x1x1 → conv2d GEMM; 3x3x3 → one merged conv2d
-        (3*O outputs) + temporal shift-add.  Only valid for the stride-1
-        units (everything but the stem)."""
-        kt = self.kernel[0]
-        w5 = self.conv.weight
-        bias = self.conv.bias
-        if kt == 1:
-            w2 = cached_cl_weight(self, 'w2', w5, lambda: w5[:, :, 0])
-            if (self.kernel[1] == 1 and xf.is_cuda
-                    and xf.dtype == torch.bfloat16
-                    and not isinstance(self.bn, nn.BatchNorm3d)
-                    and w5.shape[1] % 8 == 0 and ops.hip_available()
-                    and xf.is_contiguous(memory_format=torch.channels_last)):
-                # folded 1x1x1 conv (+bias+ReLU) as ONE fused MFMA GEMM on
-                # the CL view: removes MIOpen's SubTensor zero-fill, the
-                # bias pass, and the separate ReLU round trip
-                return ops.conv1x1_act(
-                    xf, w2, bias, 'relu' if self.activation else 'none')
-            x = ops.conv2d_act(xf, w2, bias,
-                               1, (self.kernel[1] // 2, self.kernel[2] // 2))
-        else:  # 3x3x3, stride 1
-            o = w5.shape[0]
-            wcat = cached_cl_weight(
-                self, 'wcat', w5,
-                lambda: w5.permute(2, 0, 1, 3, 4).reshape(
-                    3 * o, w5.shape[1], self.kernel[1], self.kernel[2]))
-            if bias is not None:
-                def mk_bcat():
-                    bc = torch.zeros(3 * o, device=bias.device,
-                                     dtype=bias.dtype)
-                    bc[o:2 * o] = bias
-                    return bc
-                bcat = cached_cl_weight(self, 'bcat', bias, mk_bcat)
-            else:
-                bcat = None
-            # merged-tap 3x3 conv (3*O outputs) through the in-tree
-            # implicit-GEMM kernel (1.6-1.9x MIOpen on the I3D shapes,
-            # gpurun_out/bench_conv_r2b.log)
-            y = ops.conv2d_act(xf, wcat, bcat,
-                               1, (self.kernel[1] // 2, self.kernel[2] // 2))
-            if self.activation and not isinstance(self.bn, nn.BatchNorm3d):
-                # BN folded: ReLU rides the merge kernel's epilogue
-                return temporal_merge(y, b, kt=3, st=1, p0=1, bias_tap=1,
-                                      relu=True)
-            x = temporal_merge3(y, b)
-        if isinstance(self.bn, nn.BatchNorm3d):
-            # BatchNorm3d == BatchNorm2d per channel on the flattened view
-            bn = self.bn
-            x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight,
-                             bn.bias, bn.training, bn.momentum, bn.eps)
-        return F.relu(x, inplace=True) if self.activation else x
+        module comment) through ``conv3d_flat``: 1x1x1 → conv2d GEMM; 3x3x3
+        and the 7x7x7/2 stem → one merged conv2d (kt*O outputs, 1.6-1.9x
+        MIOpen on the I3D shapes) + temporal shift-add.  With the BN folded
+        the ReLU rides the GEMM's or the merge kernel's epilogue."""
+        pads = None
+        if not self.static_same:
+            dims = (xf.shape[0] // b, *xf.shape[2:])
+            pads = [_same_pad_1d(n, k, s)
+                    for n, k, s in zip(dims, self.kernel, self.stride)]
+        fuse = self.activation and not isinstance(self.bn, nn.BatchNorm3d)
+        x = conv3d_flat(self.conv, xf, b, pads=pads,
+                        act='relu' if fuse else 'none')
+        return flat_bn_act(x, self.bn, self.activation and not fuse)
 
 
 class MaxPool3dSame(nn.Module):
@@ -227,49 +184,10 @@ class I3D(nn.Module):
 
     def _backbone(self, x: torch.Tensor) -> torch.Tensor:
         b = x.shape[0]
-        stem = self.conv3d_1a_7x7
-        if (x.is_cuda and x.dtype == torch.bfloat16 and ops.hip_available()
-                and not ops._env_flag('VFA_NO_CONV')):
-            # stem 7x7x7/2 decomposed like the 3x3x3 units: flatten time,
-            # ONE merged 7-tap conv2d (channel-padded C=3/2 -> 8, through
-            # the in-tree implicit-GEMM kernel) + strided temporal
-            # shift-add — the last real conv3d (MIOpen/CK) is gone
-            t, hh, ww = x.shape[2:]
-            xf = flatten_time(x)
-            w5 = stem.conv.weight              # (64, C, 7, 7, 7)
-            cin = w5.shape[1]
-            c8 = (cin + 7) // 8 * 8
-            wcat = cached_cl_weight(
-                stem, 'stem_wcat', w5,
-                lambda: F.pad(
-                    w5.permute(2, 0, 1, 3, 4).reshape(7 * 64, cin, 7, 7),
-                    (0, 0, 0, 0, 0, c8 - cin)))
-            bias = stem.conv.bias
-            if bias is not None:
-                def mk_b():
-                    z = torch.zeros(7 * 64, device=bias.device,
-                                    dtype=bias.dtype)
-                    # tap 3 is valid at every output position for the
-                    # TF-SAME (front 2/3) stride-2 temporal pad
-                    z[3 * 64:4 * 64] = bias
-                    return z
-                bcat = cached_cl_weight(stem, 'stem_bcat', bias, mk_b)
-            else:
-                bcat = None
-            pt = _same_pad_1d(t, 7, 2)
-            ph = _same_pad_1d(hh, 7, 2)
-            pw = _same_pad_1d(ww, 7, 2)
-            y = ops.conv2d_act(xf, wcat, bcat, 2,
-                               (ph[0], ph[1], pw[0], pw[1]))
-            bn_folded = not isinstance(stem.bn, nn.BatchNorm3d)
-            xf = temporal_merge(y, b, kt=7, st=2, p0=pt[0], bias_tap=3,
-                                relu=bn_folded, p1=pt[1])
-            if not bn_folded:
-                bn = stem.bn
-                xf = F.relu(
-                    F.batch_norm(xf, bn.running_mean, bn.running_var,
-                                 bn.weight, bn.bias, False, bn.momentum,
-                                 bn.eps), inplace=True)
+        if ops.native_ready(x, knob='VFA_NO_CONV'):
+            # the 7x7x7/2 stem decomposed like the 3x3x3 units (channel-
+            # padded C=3/2 -> 8): the last real conv3d (MIOpen/CK) is gone
+            xf = self.conv3d_1a_7x7.forward_flat(flatten_time(x), b)
         else:
             x = self.conv3d_1a_7x7(x)          # CPU path: real conv3d
             xf = flatten_time(x)               # (B*T, C, H, W) CL

@@ -248,19 +248,14 @@ class PWCNet(nn.Module):
     def _nhwc(self, x: torch.Tensor) -> bool:
         """Channels_last end to end: the dense-buffer path on the GPU in
         bf16 with the extension loaded, unless VFA_NO_PWC_NHWC=1."""
-        return (self._dense(x) and x.is_cuda and x.dtype == torch.bfloat16
-                and ops.hip_available()
-                and not ops._env_flag('VFA_FORCE_TORCH_OPS')
-                and not ops._env_flag('VFA_NO_PWC_NHWC'))
+        return self._dense(x) and ops.native_ready(x, knob='VFA_NO_PWC_NHWC')
 
     def _dense(self, x: torch.Tensor) -> bool:
-        if ops._env_flag('VFA_NO_PWC_CL'):
+        if ops.env_flag('VFA_NO_PWC_CL'):
             return False
         if self.dense_buffer is not None:
             return bool(self.dense_buffer)
-        return (x.is_cuda and x.dtype == torch.bfloat16
-                and ops.hip_available()
-                and not ops._env_flag('VFA_FORCE_TORCH_OPS'))
+        return ops.native_ready(x)
 
     def forward(self, im1: torch.Tensor, im2: torch.Tensor) -> torch.Tensor:
         """uint8-range RGB (B, 3, H, W) pairs → (B, 2, H, W) flow in input

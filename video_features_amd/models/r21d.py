@@ -16,16 +16,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import ops
-from ._flat3d import (flatten_time, temporal_merge, temporal_select,
-                      cached_cl_weight)
-
-
-def _flat_bn_relu(x, bn, relu: bool):
-    if isinstance(bn, nn.BatchNorm3d):
-        x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight,
-                         bn.bias, bn.training, bn.momentum, bn.eps)
-    return F.relu(x, inplace=True) if relu else x
+from ._flat3d import flatten_time, conv3d_flat, flat_bn_act
 
 
 def _midplanes(in_planes: int, out_planes: int, t: int = 3, k: int = 3) -> int:
@@ -53,35 +44,12 @@ class Conv2Plus1D(nn.Module):
         spatial (1,3,3) conv = conv2d; temporal (3,1,1) conv = merged
         3-tap 1x1 conv2d + shifted (strided) temporal add (with the
         follow-up ReLU fused into the merge when requested)."""
-        ss = self.spatial.stride[1]
-        sw = cached_cl_weight(self, 'sw', self.spatial.weight,
-                              lambda: self.spatial.weight[:, :, 0])
-        y = ops.conv2d_act(xf, sw, self.spatial.bias, ss, 1)
-        y = _flat_bn_relu(y, self.bn, True)
-        w = self.temporal.weight                   # (O, M, 3, 1, 1)
-        o, mid = w.shape[0], w.shape[1]
-        # R(2+1)D mid-planes (144/230/460/921...) are often not %8; on GPU
-        # the weight is zero-padded to c8 once (cached) and the conv
-        # kernel's pad pass widens the input — in-tree instead of MIOpen
-        c8 = ((mid + 7) // 8 * 8
-              if w.is_cuda and w.dtype == torch.bfloat16 else mid)
-        wcat = cached_cl_weight(
-            self, 'wcat', w,
-            lambda: F.pad(
-                w.permute(2, 0, 1, 3, 4).reshape(3 * o, mid, 1, 1),
-                (0, 0, 0, 0, 0, c8 - mid)))
-        bias = self.temporal.bias
-        if bias is not None:
-            def mk_bcat():
-                bc = torch.zeros(3 * o, device=bias.device, dtype=bias.dtype)
-                bc[o:2 * o] = bias
-                return bc
-            bcat = cached_cl_weight(self, 'bcat', bias, mk_bcat)
-        else:
-            bcat = None
-        y = ops.conv2d_act(y, wcat, bcat)
-        return temporal_merge(y, b, kt=3, st=self.temporal.stride[0], p0=1,
-                              relu=relu_after)
+        # the spatial ReLU stays a separate in-place pass even with the
+        # BN folded (fusing it is an open item, ROADMAP.md); the mid-planes
+        # (144/230/460/921...) are often not % 8 and get channel-padded
+        y = flat_bn_act(conv3d_flat(self.spatial, xf, b), self.bn, True)
+        return conv3d_flat(self.temporal, y, b,
+                           act='relu' if relu_after else 'none')
 
 
 class R21DBlock(nn.Module):
@@ -112,21 +80,15 @@ class R21DBlock(nn.Module):
         if self.downsample is None:
             identity = xf
         else:
-            conv, bn = self.downsample[0], self.downsample[1]
-            st = conv.stride[0]
             # 1x1x1 stride-s conv: temporal subsample, then conv2d stride s
-            identity = temporal_select(xf, b, st)
-            dw = cached_cl_weight(self, 'dw', conv.weight,
-                                  lambda: conv.weight[:, :, 0])
-            identity = ops.conv2d_act(identity, dw, conv.bias,
-                                      conv.stride[1], 0)
-            identity = _flat_bn_relu(identity, bn, False)
+            identity = flat_bn_act(conv3d_flat(self.downsample[0], xf, b),
+                                   self.downsample[1], False)
         bn1_folded = isinstance(self.bn1, nn.Identity)
         out = self.conv1.forward_flat(xf, b, relu_after=bn1_folded)
         if not bn1_folded:
-            out = _flat_bn_relu(out, self.bn1, True)
+            out = flat_bn_act(out, self.bn1, True)
         out = self.conv2.forward_flat(out, b)
-        out = _flat_bn_relu(out, self.bn2, False)
+        out = flat_bn_act(out, self.bn2, False)
         return F.relu(out + identity, inplace=True)
 
 
@@ -167,36 +129,10 @@ class R2Plus1D18(nn.Module):
         # stem: (1,7,7)/s(1,2,2) conv2d -> BN+ReLU -> 3-tap temporal 1x1
         sc0, sbn0, sc1, sbn1 = (self.stem[0], self.stem[1], self.stem[3],
                                 self.stem[4])
-        stem_c8 = (8 if sc0.weight.is_cuda
-                   and sc0.weight.dtype == torch.bfloat16 else 3)
-        s0w = cached_cl_weight(
-            self, 's0w', sc0.weight,
-            lambda: F.pad(sc0.weight[:, :, 0], (0, 0, 0, 0, 0, stem_c8 - 3)))
-        xf = ops.conv2d_act(xf, s0w, sc0.bias, 2, 3)
-        xf = _flat_bn_relu(xf, sbn0, True)
-        o, mid = sc1.weight.shape[0], sc1.weight.shape[1]
-        c8 = ((mid + 7) // 8 * 8
-              if sc1.weight.is_cuda and sc1.weight.dtype == torch.bfloat16
-              else mid)
-        wcat = cached_cl_weight(
-            self, 's1w', sc1.weight,
-            lambda: F.pad(
-                sc1.weight.permute(2, 0, 1, 3, 4).reshape(3 * o, mid, 1, 1),
-                (0, 0, 0, 0, 0, c8 - mid)))
-        if sc1.bias is not None:
-            def mk_bcat():
-                bc = torch.zeros(3 * o, device=sc1.bias.device,
-                                 dtype=sc1.bias.dtype)
-                bc[o:2 * o] = sc1.bias
-                return bc
-            bcat = cached_cl_weight(self, 's1b', sc1.bias, mk_bcat)
-        else:
-            bcat = None
+        xf = flat_bn_act(conv3d_flat(sc0, xf, b), sbn0, True)
         sbn1_folded = isinstance(sbn1, nn.Identity)
-        xf = temporal_merge(ops.conv2d_act(xf, wcat, bcat), b, kt=3, st=1,
-                            p0=1, relu=sbn1_folded)
-        if not sbn1_folded:
-            xf = _flat_bn_relu(xf, sbn1, True)
+        xf = conv3d_flat(sc1, xf, b, act='relu' if sbn1_folded else 'none')
+        xf = flat_bn_act(xf, sbn1, not sbn1_folded)
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
                 xf = blk.forward_flat(xf, b)

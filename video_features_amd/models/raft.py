@@ -225,9 +225,7 @@ class BasicMotionEncoder(nn.Module):
                 out_off: int = 0):
         c1 = ops.conv2d_mod(self.convc1, corr, 'relu')
         f1 = ops.conv2d_mod(self.convf1, flow, 'relu')
-        if (out is not None and c1.is_cuda and c1.dtype == torch.bfloat16
-                and ops.hip_available()
-                and c1.is_contiguous(memory_format=torch.channels_last)):
+        if out is not None and ops.native_ready(c1, channels_last=True):
             # cat-free path: convc2/convf2 write their channel slices of
             # ONE buffer via the conv epilogue's ldc, and the final conv
             # writes straight into the caller's (GRU input) buffer — the

@@ -37,10 +37,8 @@ class BasicBlock(nn.Module):
                 nn.BatchNorm2d(planes))
 
     def forward(self, x):
-        if (isinstance(self.bn1, nn.Identity) and x.is_cuda
-                and x.dtype == torch.bfloat16
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and ops.hip_available()):
+        if (isinstance(self.bn1, nn.Identity)
+                and ops.native_ready(x, channels_last=True)):
             # both 3x3 convs through the in-tree implicit-GEMM kernel;
             # conv2 fuses the residual add + ReLU into its epilogue.
             # The downsample 1x1 (BN folded -> [conv, Identity]) also goes
@@ -81,11 +79,8 @@ class Bottleneck(nn.Module):
     def _fused_ready(self, x) -> bool:
         # inference path: BNs folded into the convs, bf16 channels_last on
         # GPU with the HIP extension present
-        return (isinstance(self.bn1, nn.Identity) and x.is_cuda
-                and x.dtype == torch.bfloat16
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and ops.hip_available()
-                and not ops._env_flag('VFA_NO_LTGEMM'))
+        return (isinstance(self.bn1, nn.Identity) and ops.native_ready(
+            x, knob='VFA_NO_LTGEMM', channels_last=True))
 
     def forward(self, x):
         if self._fused_ready(x):
@@ -146,9 +141,8 @@ class ResNet(nn.Module):
         x = ops.conv2d_mod(self.conv1, x, 'relu' if bn1_id else 'none')
         if not bn1_id:
             x = self.relu(self.bn1(x))
-        if (x.is_cuda and ops.hip_available()
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and ops._env_flag('VFA_STEMPOOL')):
+        if (ops.env_flag('VFA_STEMPOOL')
+                and ops.native_ready(x, channels_last=True)):
             # opt-in: the in-tree pool kernel measured ~3% SLOWER end-to-end
             # than torch's NHWC maxpool at this shape (64ch 112x112; same-box
             # A/B 32.3k vs 33.3k f/s), so torch stays the default here

@@ -27,6 +27,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import ops
+
 # ---- frontend parameters
 SAMPLE_RATE = 16000
 STFT_WINDOW_SEC = 0.025
@@ -120,10 +122,7 @@ class VGGishNet(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(N, 96, 64) log-mel examples → (N, 128) embeddings."""
         x = x[:, None]
-        if (x.is_cuda and x.dtype == torch.bfloat16
-            and __import__('video_features_amd.ops', fromlist=['o'])
-                .hip_available()):
-            from .. import ops
+        if ops.native_ready(x):
             # conv+ReLU pairs through the in-tree implicit-GEMM kernel
             # (first conv has C=1 → eager fallback inside conv2d_mod)
             x = x.contiguous(memory_format=torch.channels_last)

@@ -22,7 +22,7 @@ _ext = None
 _ext_err: Optional[str] = None
 
 
-def _env_flag(name: str) -> bool:
+def env_flag(name: str) -> bool:
     """Boolean env knob: '', '0', 'false', 'no', 'off' (any case) are False —
     so VFA_X=0 really disables (documented knob-table semantics)."""
     return os.environ.get(name, '').strip().lower() not in (
@@ -48,7 +48,7 @@ def hip_available() -> bool:
 def _use_hip(t: torch.Tensor) -> bool:
     if not t.is_cuda:
         return False
-    if _env_flag('VFA_FORCE_TORCH_OPS'):
+    if env_flag('VFA_FORCE_TORCH_OPS'):
         return False
     ext = _load_extension()
     if ext is None:
@@ -58,6 +58,20 @@ def _use_hip(t: torch.Tensor) -> bool:
             '`python setup.py build_ext --inplace` (PYTORCH_ROCM_ARCH=gfx950). '
             'Refusing to fall back to eager PyTorch on a GPU run.')
     return True
+
+
+def native_ready(x: torch.Tensor, *, knob: Optional[str] = None,
+                 channels_last: bool = False) -> bool:
+    """The one answer to "does ``x`` take a model's in-tree bf16 path?":
+    a bf16 GPU tensor with the extension loaded, ``VFA_FORCE_TORCH_OPS`` and
+    the opt-out ``knob`` (if given) unset and, with ``channels_last``, that
+    layout.  Never raises: a model asks it once and takes its fused or its
+    module path as a whole; ``_use_hip`` does the raising inside each op."""
+    return bool(x.is_cuda and x.dtype == torch.bfloat16 and hip_available()
+                and not env_flag('VFA_FORCE_TORCH_OPS')
+                and not (knob and env_flag(knob))
+                and (not channels_last or (x.dim() == 4 and x.is_contiguous(
+                    memory_format=torch.channels_last))))
 
 
 # the dtypes the dtype-generic kernels instantiate (dispatch_dtype)
@@ -92,15 +106,19 @@ def _slice_width(name: str, x: torch.Tensor, in_off: int,
     return in_ch
 
 
-def _cached_weight(module: torch.nn.Module, attr: str, key_extra, make):
-    """``make()`` of ``module.weight``, cached on the module as ``attr`` and
-    keyed on the weight's version (a later load_state_dict invalidates),
-    dtype, device, pointer and ``key_extra``."""
-    w = module.weight
-    key = (w._version, w.dtype, w.device, w.data_ptr(), key_extra)
+def derived(module: torch.nn.Module, attr: str, params, make, extra=None):
+    """``make()`` — tensors derived from ``params`` (None entries skipped) —
+    cached on ``module`` as ``attr`` = (key, value).  The key holds every
+    parameter's version (an in-place write such as load_state_dict
+    invalidates), dtype, device and pointer (``.to()`` replaces them), and
+    ``extra``.  ``make`` runs under ``no_grad``: what is cached never hangs
+    on an autograd graph."""
+    key = tuple((p._version, p.dtype, p.device, p.data_ptr())
+                for p in params if p is not None) + (extra,)
     ent = getattr(module, attr, None)
     if ent is None or ent[0] != key:
-        ent = (key, make())
+        with torch.no_grad():
+            ent = (key, make())
         setattr(module, attr, ent)
     return ent[1]
 
@@ -385,7 +403,7 @@ def corr_lookup(pyramid, coords: torch.Tensor, radius: int = 4,
     if _use_hip(coords) and radius == 4:
         return _ext.corr_lookup(list(pyramid), coords.contiguous(), nhwc,
                                 out_dtype,
-                                _env_flag('VFA_CORR_GMEM'))
+                                env_flag('VFA_CORR_GMEM'))
     # torch reference: per-level grid_sample of the displacement window
     b, _, h, w = coords.shape
     r = radius
@@ -636,7 +654,7 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor,
     n = weight.shape[0]
     if (_use_hip(x) and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16 and k % 8 == 0 and n >= 16
-            and not _env_flag('VFA_NO_LTGEMM')):
+            and not env_flag('VFA_NO_LTGEMM')):
         x2 = x.reshape(-1, k).contiguous()
         r2 = res.reshape(-1, n).contiguous() if res is not None else None
         out = _ext.linear_act(x2, weight.contiguous(), bias, r2,
@@ -663,10 +681,9 @@ def fused_ln_tiles(x: torch.Tensor, weight: torch.Tensor) -> bool:
     full 256x256x64 tiles.  Anything else takes their torch composition."""
     k, n = x.shape[-1], weight.shape[0]
     m = x.numel() // max(k, 1)
-    return bool(x.is_cuda and x.dtype == torch.bfloat16
+    return bool(native_ready(x, knob='VFA_NO_LTGEMM')
                 and weight.dtype == torch.bfloat16
-                and m > 0 and m % 256 == 0 and n % 256 == 0 and k % 64 == 0
-                and not _env_flag('VFA_NO_LTGEMM') and _use_hip(x))
+                and m > 0 and m % 256 == 0 and n % 256 == 0 and k % 64 == 0)
 
 
 def linear_res_stats(x: torch.Tensor, weight: torch.Tensor,
@@ -813,7 +830,7 @@ def conv2d_act(x: torch.Tensor, weight: torch.Tensor,
             and (in_ch is None or (in_ch % 8 == 0 and in_off % 8 == 0
                                    and x.shape[1] % 8 == 0))
             and x.is_contiguous(memory_format=torch.channels_last)
-            and not _env_flag('VFA_NO_CONV')):
+            and not env_flag('VFA_NO_CONV')):
         if (weight.shape[2] == 1 and weight.shape[3] == 1
                 and (sh, sw) == (1, 1) and (pt, pb, pl, pr) == (0, 0, 0, 0)
                 and weight.shape[1] == x.shape[1] and out is None
@@ -873,12 +890,8 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
     sliced = in_off is not None
     c = conv.in_channels if sliced else x.shape[1]
     c8 = (c + 7) // 8 * 8
-    eligible = (x.is_cuda and x.dtype == torch.bfloat16
-                and w.dtype == torch.bfloat16
-                and conv.groups == 1
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and hip_available() and not _env_flag('VFA_NO_CONV')
-                and not _env_flag('VFA_FORCE_TORCH_OPS'))
+    eligible = (native_ready(x, knob='VFA_NO_CONV', channels_last=True)
+                and w.dtype == torch.bfloat16 and conv.groups == 1)
     if eligible and sliced:
         _slice_width('conv2d_mod', x, in_off, c8, aligned=True)
     kw_slice = dict(in_off=in_off, in_ch=c8) if sliced else {}
@@ -894,10 +907,10 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
         # input also gets its input channels padded to the slice width.
         kout = w.shape[0]
         cpad = c8 - c if sliced else 0
-        wp, bp = _cached_weight(conv, '_vfa_wnpad', cpad, lambda: (
+        wp, bp = derived(conv, '_vfa_wnpad', (w, conv.bias), lambda: (
             padded(cpad, 16 - kout),
             torch.nn.functional.pad(conv.bias, (0, 16 - kout))
-            if conv.bias is not None else None))
+            if conv.bias is not None else None), cpad)
         y = conv2d_act(x, wp, bp, conv.stride, conv.padding, act,
                        dilation=conv.dilation, **kw_slice)[:, :kout]
         if out is None:
@@ -908,8 +921,8 @@ def conv2d_mod(conv: torch.nn.Module, x: torch.Tensor, act: str = 'none',
         # channel dim is zero-padded once and cached; the input is padded
         # inside the conv's (fused) pad pass, or, as a slice, read in place
         # at the padded width
-        wp = w if c % 8 == 0 else _cached_weight(
-            conv, '_vfa_wpad', None, lambda: padded(c8 - c, 0))
+        wp = w if c % 8 == 0 else derived(
+            conv, '_vfa_wpad', (w,), lambda: padded(c8 - c, 0))
         return conv2d_act(x, wp, conv.bias, conv.stride, conv.padding, act,
                           res, out, out_off, conv.dilation, **kw_slice)
     y = conv(x[:, in_off:in_off + c] if sliced else x)
@@ -970,11 +983,10 @@ def _tconv_kernel_ok(x: torch.Tensor, weight: torch.Tensor, stride, padding
     """The geometry, dtype and device tconv.hip covers (layout aside)."""
     st = (stride, stride) if isinstance(stride, int) else tuple(stride)
     pd = (padding, padding) if isinstance(padding, int) else tuple(padding)
-    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+    return (native_ready(x, knob='VFA_NO_TCONV') and x.dim() == 4
             and weight.dtype == torch.bfloat16 and weight.dim() == 4
             and tuple(weight.shape[2:]) == (4, 4) and weight.shape[1] <= 2
-            and st == (2, 2) and pd == (1, 1)
-            and not _env_flag('VFA_NO_TCONV') and _use_hip(x))
+            and st == (2, 2) and pd == (1, 1))
 
 
 def _tconv_check_out(x: torch.Tensor, out: Optional[torch.Tensor],
@@ -1085,10 +1097,8 @@ def conv_transpose2d_mod(m: torch.nn.Module, x: torch.Tensor,
             _slice_width('conv_transpose2d_mod', x, in_off, c8, aligned=True)
 
         def packed(width):
-            def make():
-                with torch.no_grad():
-                    return _pack_tconv_weight(w, width)
-            return _cached_weight(m, '_vfa_tconv_wp', width, make)
+            return derived(m, '_vfa_tconv_wp', (w,),
+                           lambda: _pack_tconv_weight(w, width), width)
 
         y = _tconv_kernels(x, w, m.bias, out, out_off,
                            in_off if sliced else 0, c8 if sliced else None,
