@@ -18,6 +18,19 @@ def _hip_loaded():
     return ops
 
 
+ACT_ID = {'none': 0, 'relu': 1, 'quick_gelu': 2, 'gelu': 3, 'leaky_relu': 4}
+
+
+def _assert_route(ops, m, n, k, act, want):
+    """The kernel linear_act picks (ops._ext.linear_route, the host
+    function the launchers call): routing drift fails here instead of
+    silently moving the case to another kernel."""
+    got = ops._ext.linear_route(m, n, k, ACT_ID[act]).split(':')[0]
+    assert got == want, (
+        f'{(m, n, k)} act={act} is meant to run the {want} route but goes '
+        f'to {got}: change the SHAPE so it reaches its route')
+
+
 def _ref(x, w, b, act):
     y = torch.nn.functional.linear(x.float(), w.float(),
                                    b.float() if b is not None else None)
@@ -65,6 +78,7 @@ def test_linear_act(dev, m, n, k, act):
 def test_linear_thin_streaming(dev, m, n, k, act):
     """The M-huge / K-shallow streaming kernel (1x1-conv-as-GEMM shapes)."""
     ops = _hip_loaded()
+    _assert_route(ops, m, n, k, act, 'thin')
     torch.manual_seed(0)
     x = (torch.randn(m, k, device=dev) / (k ** 0.25)).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev) / (k ** 0.25)).to(torch.bfloat16)
@@ -74,6 +88,19 @@ def test_linear_thin_streaming(dev, m, n, k, act):
     err = (out.float() - ref).abs()
     rel = err.max().item() / max(ref.abs().max().item(), 1e-6)
     assert rel < 3e-2, rel
+
+
+# Where these shapes run today.  The persistent kernel has since taken
+# every problem of >= 150 tiles and the 8-phase kernel keeps act-none
+# problems of 64..149 full tiles, so one case is left on it by default;
+# test_gpu_gemm_epilogue.py::test_forced_route_child and
+# test_gpu_gemm_exact.py run it on purpose.
+ROUTE_8PHASE = {
+    (19200, 2304, 768): ('256p', '256p'),
+    (19200, 768, 3072): ('256p', '256p'),
+    (4096, 2048, 768): ('8p', 'small'),
+    (4096, 256, 192): ('small', 'small'),
+}
 
 
 @pytest.mark.parametrize('m,n,k', [
@@ -87,6 +114,8 @@ def test_linear_8phase(dev, m, n, k, act):
     """The deep-pipelined 256^2 kernel (full tiles, counted-vmcnt raw
     barriers); numerics vs fp32 torch."""
     ops = _hip_loaded()
+    _assert_route(ops, m, n, k, act,
+                  ROUTE_8PHASE[(m, n, k)][act != 'none'])
     torch.manual_seed(0)
     x = (torch.randn(m, k, device=dev) / (k ** 0.25)).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev) / (k ** 0.25)).to(torch.bfloat16)
@@ -104,6 +133,7 @@ def test_linear_8phase_residual(dev):
     ops = _hip_loaded()
     torch.manual_seed(4)
     m, n, k = 19200, 768, 3072
+    _assert_route(ops, m, n, k, 'none', '256p')   # 225 tiles: persistent
     x = (torch.randn(m, k, device=dev) / 8).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev) / 8).to(torch.bfloat16)
     b = torch.randn(n, device=dev).to(torch.bfloat16)
@@ -119,6 +149,7 @@ def test_linear_thin_residual(dev):
     ops = _hip_loaded()
     torch.manual_seed(3)
     m, n, k = 131072, 256, 64
+    _assert_route(ops, m, n, k, 'relu', 'thin')
     x = (torch.randn(m, k, device=dev) / 2).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev) / 2).to(torch.bfloat16)
     b = torch.randn(n, device=dev).to(torch.bfloat16)

@@ -55,8 +55,19 @@ def _problem(m, n, k):
     return x, w, b, r, y
 
 
-def _check(m, n, k, act, bias=True, res=False):
+ACT_ID = {'none': 0, 'relu': 1, 'quick_gelu': 2, 'gelu': 3, 'leaky_relu': 4}
+
+
+def _check(m, n, k, act, bias=True, res=False, route=None):
+    """route: the kernel the case is meant for, asserted through
+    ops._ext.linear_route (the host function the launchers call) so that
+    routing drift fails instead of silently emptying the case."""
     ops = _ops()
+    if route is not None:
+        got = ops._ext.linear_route(m, n, k, ACT_ID[act])
+        assert got == route, (
+            f'{(m, n, k)} act={act} is meant to run the {route} route but '
+            f'goes to {got}: change the SHAPE so it reaches its route')
     x, w, b, r, y = _problem(m, n, k)
     out = ops.linear_act(x, w, b if bias else None, act, r if res else None)
     assert out.shape == (m, n) and out.dtype == torch.bfloat16
@@ -91,7 +102,9 @@ PERSISTENT_SHAPES = [
 @gpu
 @pytest.mark.parametrize('m,n,k', PERSISTENT_SHAPES)
 def test_tile_walk(m, n, k):
-    _check(m, n, k, 'quick_gelu')
+    route = ('256p+edge' if n % 256 else '256p') if k % 64 == 0 \
+        else 'big_guard'
+    _check(m, n, k, 'quick_gelu', route=route)
 
 
 @gpu
@@ -100,20 +113,24 @@ def test_tile_walk(m, n, k):
 @pytest.mark.parametrize('act', ACTS)
 @pytest.mark.parametrize('m,n,k', [(4352, 4096, 128), (2560, 3848, 128)])
 def test_epilogue_specialisations(m, n, k, act, bias, res):
-    _check(m, n, k, act, bias, res)
+    _check(m, n, k, act, bias, res,
+           route='256p+edge' if n % 256 else '256p')
 
 
 @gpu
 @pytest.mark.parametrize('m,n,k', [(256, 128, 64), (333, 100, 72)])
 def test_leaky_relu_small_tile(m, n, k):
-    _check(m, n, k, 'leaky_relu')
+    _check(m, n, k, 'leaky_relu', route='small')
 
 
 @gpu
 @pytest.mark.parametrize('act', ACTS)
 @pytest.mark.parametrize('m,n,k', [(4096, 2048, 768), (4096, 256, 192)])
 def test_8phase_shapes(m, n, k, act):
-    _check(m, n, k, act, True, True)
+    # by default only act none on the 128-tile shape is the 8-phase
+    # kernel's (64..149 full tiles); test_forced_route_child runs the rest
+    route = '8p' if (n == 2048 and act == 'none') else 'small'
+    _check(m, n, k, act, True, True, route=route)
 
 
 _CHILD = r'''

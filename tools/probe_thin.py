@@ -24,6 +24,6 @@ with torch.cuda.graph(g):
     ops.linear_act(x,w,b,'relu',r)
 print('graph  :', t(lambda: g.replay()), 'us')
 # conv1x1_act route (as the model calls it)
-xc = x.reshape(768,56,56,64).permute(0,3,1,2)
-rc = r.reshape(768,56,56,256).permute(0,3,1,2)
+xc = x.reshape(m // (56*56),56,56,k).permute(0,3,1,2)
+rc = r.reshape(m // (56*56),56,56,n).permute(0,3,1,2)
 print('conv1x1:', t(lambda: ops.conv1x1_act(xc, w.reshape(n,k,1,1), b, 'relu', rc)), 'us')

@@ -511,6 +511,20 @@ torch::Tensor linear_act(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// name of the kernel route linear_act takes for (m, n, k, act) — the same
+// host function the launchers call, so tests can pin a case to a kernel.
+// The thin route reads "thin:<nch>" with its N-chunk.
+std::string linear_route(int64_t m, int64_t n, int64_t k, int64_t act) {
+  TORCH_CHECK(m > 0 && n > 0 && k > 0 && m <= INT_MAX && n <= INT_MAX &&
+              k <= INT_MAX && k % 8 == 0 && act >= 0 && act <= 4);
+  static const char* const names[] = {"thin", "8p", "256p", "256p+edge",
+                                      "big_guard", "small"};
+  int nch = 0;
+  const int r = vfa_linear_route((int)m, (int)n, (int)k, (int)act, &nch);
+  std::string s = names[r];
+  return r == VFA_ROUTE_THIN ? s + ":" + std::to_string(nch) : s;
+}
+
 // the fused LayerNorm-fold epilogues exist for full 256^2 tiles only
 static void check_full_tiles(const char* op, int m, int n, int k) {
   TORCH_CHECK(m > 0 && m % 256 == 0 && n % 256 == 0 && k % 64 == 0, op,
@@ -884,6 +898,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool3d_same", &maxpool3d_same);
   m.def("maxpool2d_same", &maxpool2d_same);
   m.def("linear_act", &linear_act);
+  m.def("linear_route", &linear_route);
   m.def("linear_res_stats", &linear_res_stats);
   m.def("linear_ln_act", &linear_ln_act);
   m.def("conv2d_nhwc", &conv2d_nhwc);

@@ -609,13 +609,13 @@ void linear8p_kernel(const __bf16* __restrict__ a,
     epilogue_strips<ACT, false>(acc, ep, bias, res, c, n, row0, col0, lane);
 }
 
+// caller: vfa_linear_route said VFA_ROUTE_8P (full tiles, k / 64 >= 3, at
+// least 64 tiles)
 template <int ACT>
-bool launch_8p(const void* a, const void* w, const void* bias,
+void launch_8p(const void* a, const void* w, const void* bias,
                const void* res, void* c, int m, int n, int k,
                hipStream_t stream) {
-  if (m % 256 || n % 256 || k % 64 || k / 64 < 3) return false;
   const long long tiles = (long long)(m / 256) * (n / 256);
-  if (tiles < 64) return false;              // chip fill
   static bool attr_set[5] = {};
   if (!attr_set[ACT]) {
     (void)hipFuncSetAttribute(
@@ -628,7 +628,6 @@ bool launch_8p(const void* a, const void* w, const void* bias,
                      (const __bf16*)w, (const __bf16*)bias,
                      (const __bf16*)res, (__bf16*)c, m, n, k, m / 256,
                      n / 256);
-  return true;
 }
 
 // ------------------------------------------------------- thin-K streaming
@@ -640,6 +639,8 @@ bool launch_8p(const void* a, const void* w, const void* bias,
 // global -> MFMA fragments (A is read ONCE for all N columns), grid-strides
 // over M, and has no per-K barriers.  vgpr budget: A frags 2*K/32*4 +
 // B frags K/32*4 + acc 8 -> ~130 at K=256 (2 blocks/CU).
+constexpr int THIN_ET_BYTES = 8 * 64 * 4;    // one wave's f32 epilogue tile
+
 template <int ACT, int KF>
 __global__ __launch_bounds__(256, 2)
 void linear_thin_kernel(const __bf16* __restrict__ a,
@@ -661,14 +662,28 @@ void linear_thin_kernel(const __bf16* __restrict__ a,
   const int lo = lane & 15, hi4 = lane >> 4;
 
   // LDS layout: W chunk (rows of KC+8 elems, breaks the ds_read bank
-  // pattern; K..KC zero-filled) + per-wave 16x64 bf16 epilogue tiles
+  // pattern; K..KC zero-filled) + per-wave 8x64 f32 epilogue tiles
+  // (THIN_ET_BYTES each).  The tiles hold f32 accumulators, so bias,
+  // residual and activation are applied in f32 and the result is rounded
+  // to bf16 once, as in epilogue_strips.  8 rows, not that one's 16: the
+  // four tiles (8 KiB) then take no more LDS than the bf16 tiles they
+  // replace and the N-chunk stays what it was.  A 16-row MFMA tile goes
+  // through in two passes q of 8 rows, hi4 * 4 + q * 2 + {0, 1} (a lane
+  // holds rows hi4 * 4 + 0..3, so every lane writes in both passes).
+  // Tile row t = hi4 * 2 + {0, 1}; with b = (t >> 1) & 1, column c sits at
+  // c ^ b * 20: the 16 of it puts the two hi4 lane groups of a 32-lane
+  // ds_write_b32 group on disjoint halves of the 32 banks; the 4 of it
+  // swaps the 16-B halves of an 8-column segment on tile rows 2, 3 (mod
+  // 4), so the 16 lanes a ds_read_b128 serves at a time -- 4 segments on
+  // each of 4 consecutive rows, all at the same offset mod 64 banks --
+  // cover the 64 banks exactly once.
   extern __shared__ __attribute__((aligned(16))) char smem_t[];
   __bf16* wl = reinterpret_cast<__bf16*>(smem_t);
   constexpr int LDW = KC + 8;
   const int n0 = blockIdx.y * nch;
   const int ncols = min(nch, n - n0);
-  __bf16* et = reinterpret_cast<__bf16*>(smem_t) + (long long)nch * LDW +
-               wave * 16 * 72;
+  float* et = reinterpret_cast<float*>(smem_t + (size_t)nch * LDW * 2) +
+              wave * (THIN_ET_BYTES / 4);
   for (int t = threadIdx.x; t < ncols * (KC / 8); t += 256) {
     const int row = t / (KC / 8), seg = t % (KC / 8);
     uint4 v = {0u, 0u, 0u, 0u};
@@ -727,49 +742,61 @@ void linear_thin_kernel(const __bf16* __restrict__ a,
       const int jcols = min(64, ncols - j0);   // columns this step
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) {
-        // fragment -> LDS tile (2-B writes; wave-local, no barrier)
+        // fragment -> LDS -> (row, 8-col seg) per lane, in f32, 8 rows
+        // per pass (wave-local, no barrier); 16-B res loads + stores on
+        // 128-B-contiguous rows
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
+        for (int q = 0; q < 2; ++q) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            et[(hi4 * 4 + r) * 72 + jj * 16 + lo] =
-                (__bf16)acc[mi][jj][r];
-        __builtin_amdgcn_s_waitcnt(/*lgkmcnt(0)*/ 0xc07f);
-        // vectorized out: 2 passes x 8 rows; lane -> (row, 8-col seg),
-        // 16-B res loads + stores on 128-B-contiguous rows
+          for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const int er = p * 8 + (lane >> 3);
+            for (int r2 = 0; r2 < 2; ++r2)
+              et[(hi4 * 2 + r2) * 64 +
+                 (((jj ^ (hi4 & 1)) << 4) | (lo ^ ((hi4 & 1) << 2)))] =
+                  acc[mi][jj][q * 2 + r2];
+          __builtin_amdgcn_s_waitcnt(/*lgkmcnt(0)*/ 0xc07f);
+          const int tr = lane >> 3;                      // tile row
+          const int tb = (tr >> 1) & 1;
+          const int er = (tr >> 1) * 4 + q * 2 + (tr & 1);
           const int ec = (lane & 7) * 8;
           const long long row = r0 + mi * 16 + er;
           const int col = n0 + j0 + ec;
-          if (row >= m || ec >= jcols) continue;
-          bf16x8 v8 = *reinterpret_cast<const bf16x8*>(et + er * 72 + ec);
-          if (ec + 8 <= jcols && col + 8 <= n) {
-            bf16x8 o8;
-            bf16x8 b8{}, rr8{};
-            if (bias)
-              b8 = *reinterpret_cast<const bf16x8*>(bias + col);
-            if (res)
-              rr8 = *reinterpret_cast<const bf16x8*>(res + row * n + col);
+          if (row < m && ec < jcols) {
+            const float* src = et + tr * 64 + (ec ^ (tb << 4));
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + (tb << 2));
+            const f32x4 v1 =
+                *reinterpret_cast<const f32x4*>(src + (4 ^ (tb << 2)));
+            if (ec + 8 <= jcols && col + 8 <= n) {
+              bf16x8 o8;
+              bf16x8 b8{}, rr8{};
+              if (bias)
+                b8 = *reinterpret_cast<const bf16x8*>(bias + col);
+              if (res)
+                rr8 = *reinterpret_cast<const bf16x8*>(res + row * n + col);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float v = (float)v8[e];
-              if (bias) v += (float)b8[e];
-              if (res) v += (float)rr8[e];
-              o8[e] = (__bf16)act_f(v, ACT);
-            }
-            *reinterpret_cast<bf16x8*>(c + row * n + col) = o8;
-          } else {
-            for (int e = 0; e < 8 && ec + e < jcols && col + e < n; ++e) {
-              float v = (float)v8[e];
-              if (bias) v += (float)bias[col + e];
-              if (res) v += (float)res[row * n + col + e];
-              c[row * n + col + e] = (__bf16)act_f(v, ACT);
+              for (int e = 0; e < 8; ++e) {
+                float v = e < 4 ? v0[e & 3] : v1[e & 3];
+                if (bias) v += (float)b8[e];
+                if (res) v += (float)rr8[e];
+                o8[e] = (__bf16)act_f(v, ACT);
+              }
+              *reinterpret_cast<bf16x8*>(c + row * n + col) = o8;
+            } else {
+              // ragged segment, element-wise; e stays compile-time (a
+              // runtime-indexed vector would go to scratch)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                if (ec + e < jcols && col + e < n) {
+                  float v = e < 4 ? v0[e & 3] : v1[e & 3];
+                  if (bias) v += (float)bias[col + e];
+                  if (res) v += (float)res[row * n + col + e];
+                  c[row * n + col + e] = (__bf16)act_f(v, ACT);
+                }
+              }
             }
           }
+          __builtin_amdgcn_s_waitcnt(0xc07f);  // reads done before reuse
         }
-        if (mi == 0) __builtin_amdgcn_s_waitcnt(0xc07f);  // tile reuse
       }
     }
   }
@@ -786,23 +813,33 @@ void launch_thin_kf(const void* a, const void* w, const void* bias,
                      m, n, nch, k);
 }
 
-template <int ACT>
-bool launch_thin(const void* a, const void* w, const void* bias,
-                 const void* res, void* c, int m, int n, int k,
-                 hipStream_t stream) {
+// The thin kernel's N-chunk (W rows resident in LDS per block) for an
+// (m, n, k) problem, 0 when the kernel does not take it.
+int thin_nch(int m, int n, int k) {
   // n % 8: the vectorized epilogue's 16-B res/out accesses need 8-elem
   // row alignment.  K any multiple of 8 (<= 256): the last A fragment is
   // masked per lane, W LDS rows zero-fill to the 32-elem boundary.
-  if (k > 256 || k % 8 != 0 || k < 64 || m < 65536 || n % 8 != 0)
-    return false;
+  // K < 64: not worth MFMA
+  if (k > 256 || k % 8 != 0 || k < 64 || m < 65536 || n % 8 != 0) return 0;
   const int kc = (k + 31) / 32 * 32;
-  // W chunk + 9 KiB epilogue tiles bounded by 80 KiB LDS (2 blocks/CU)
-  const int nch_cap = 36352 / (kc + 8) / 16 * 16;
+  // W chunk + the four waves' epilogue tiles bounded by 80 KiB LDS (2
+  // blocks/CU).  9 KiB stay set aside for the tiles, 1 KiB more than
+  // they take, so the N-chunks are those the kernel was measured with.
+  static_assert(4 * THIN_ET_BYTES <= 9 * 1024, "epilogue tiles > budget");
+  const int nch_cap = (80 * 1024 - 9 * 1024) / 2 / (kc + 8) / 16 * 16;
   const int nch = min((n + 15) & ~15, nch_cap);
-  if (nch < 16) return false;
+  return nch < 16 ? 0 : nch;
+}
+
+// caller: nch = thin_nch(m, n, k) > 0, so 64 <= k <= 256
+template <int ACT>
+void launch_thin(const void* a, const void* w, const void* bias,
+                 const void* res, void* c, int m, int n, int nch, int k,
+                 hipStream_t stream) {
+  const int kc = (k + 31) / 32 * 32;
   // enough M-blocks to fill the chip; grid-stride handles the rest
   const int m_blocks = (int)min(((long long)m + 127) / 128, 4096LL);
-  const size_t lds = (size_t)nch * (kc + 8) * 2 + 4 * 16 * 72 * 2;
+  const size_t lds = (size_t)nch * (kc + 8) * 2 + 4 * THIN_ET_BYTES;
   switch (kc / 32) {
     case 2: launch_thin_kf<ACT, 2>(a, w, bias, res, c, m, n, nch, k, m_blocks, lds, stream); break;
     case 3: launch_thin_kf<ACT, 3>(a, w, bias, res, c, m, n, nch, k, m_blocks, lds, stream); break;
@@ -811,9 +848,8 @@ bool launch_thin(const void* a, const void* w, const void* bias,
     case 6: launch_thin_kf<ACT, 6>(a, w, bias, res, c, m, n, nch, k, m_blocks, lds, stream); break;
     case 7: launch_thin_kf<ACT, 7>(a, w, bias, res, c, m, n, nch, k, m_blocks, lds, stream); break;
     case 8: launch_thin_kf<ACT, 8>(a, w, bias, res, c, m, n, nch, k, m_blocks, lds, stream); break;
-    default: return false;                     // K<64: not worth MFMA
+    default: break;                            // unreachable, see thin_nch
   }
-  return true;
 }
 
 // the persistent kernel over ntiles full 256^2 tiles (tile columns
@@ -844,23 +880,23 @@ void launch_256p(const void* a, const void* w, const void* bias,
                      k, tiles_m, ntiles, x);
 }
 
+// route: what vfa_linear_route said; BIG for every route but VFA_ROUTE_SMALL
 template <int ACT, bool BIG>
 void launch_tile(const void* a, const void* w, const void* bias,
-                 const void* res, void* c, int m, int n, int k,
+                 const void* res, void* c, int m, int n, int k, int route,
                  hipStream_t stream) {
   constexpr int BM = BIG ? 256 : 128, BN = BIG ? 256 : 128;
   const int tiles_m = (m + BM - 1) / BM, tiles_n = (n + BN - 1) / BN;
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
   const bool full = (k % BK == 0);   // per-tile M/N edges handled inside
   int tile_base = 0;
-  if (BIG && full && m % 256 == 0 && n >= 256 && n % 8 == 0) {
+  if (BIG && (route == VFA_ROUTE_256P || route == VFA_ROUTE_256P_EDGE)) {
     // interior tile columns -> the persistent kernel; what is left for
     // the guarded kernel below is at most the ragged last column
-    // (n % 8: its 16-B bias/res/out vectors need 8-element row alignment)
     const int ntiles = tiles_m * (n / 256);
     launch_256p<ACT, EPI_PLAIN>(a, w, bias, res, c, n, k, tiles_m, ntiles,
                                 EpiExtra{}, stream);
-    if (n % 256 == 0) return;
+    if (route == VFA_ROUTE_256P) return;
     tile_base = ntiles;
   }
   const dim3 grid(tiles_m * tiles_n - tile_base);
@@ -882,6 +918,31 @@ template <int ACT>
 void launch_linear(const void* a, const void* w, const void* bias,
                    const void* res, void* c, int m, int n, int k,
                    hipStream_t stream) {
+  int nch = 0;
+  const int route = vfa_linear_route(m, n, k, ACT, &nch);
+  switch (route) {
+    case VFA_ROUTE_THIN:
+      launch_thin<ACT>(a, w, bias, res, c, m, n, nch, k, stream);
+      break;
+    case VFA_ROUTE_8P:
+      launch_8p<ACT>(a, w, bias, res, c, m, n, k, stream);
+      break;
+    case VFA_ROUTE_SMALL:
+      launch_tile<ACT, false>(a, w, bias, res, c, m, n, k, route, stream);
+      break;
+    default:
+      launch_tile<ACT, true>(a, w, bias, res, c, m, n, k, route, stream);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// Every routing decision of vfa_linear_act, in one place: the launchers
+// above act on what this returns, and it is bound to Python as
+// _ext.linear_route so that a test can pin a shape to its kernel.
+int vfa_linear_route(int m, int n, int k, int act, int* nch) {
   // M-huge / K-shallow -> the streaming kernel (reads A once, no K-loop
   // barriers); else BIG tiles when M tiles evenly (a half-empty 256-row
   // tail tile and the block-round quantization cost more than the smaller
@@ -896,23 +957,28 @@ void launch_linear(const void* a, const void* w, const void* bias,
   // 334-337 vs 359 — so it goes first.  The 8-phase kernel keeps the
   // act-none full-tile problems of 64..149 tiles, which the persistent
   // route does not take.  VFA_8P forces the 8-phase kernel wherever it
-  // can run, VFA_NO_8P disables it, for A/B.
+  // can run, VFA_NO_8P disables it, VFA_NO_THIN disables the streaming
+  // kernel, for A/B.
   static const int env8p = getenv("VFA_8P") ? 1
                            : getenv("VFA_NO_8P") ? -1 : 0;
-  if (launch_thin<ACT>(a, w, bias, res, c, m, n, k, stream)) return;
+  static const bool no_thin = getenv("VFA_NO_THIN") != nullptr;
+  *nch = no_thin ? 0 : thin_nch(m, n, k);
+  if (*nch) return VFA_ROUTE_THIN;
   const long long tiles = (long long)((m + 255) / 256) * ((n + 255) / 256);
   const bool big = n >= 256 && m % 256 == 0 && tiles >= 150;
-  const bool want8p = env8p > 0 || (env8p == 0 && ACT == 0 && !big);
-  if (want8p && launch_8p<ACT>(a, w, bias, res, c, m, n, k, stream)) return;
-  if (big)
-    launch_tile<ACT, true>(a, w, bias, res, c, m, n, k, stream);
-  else
-    launch_tile<ACT, false>(a, w, bias, res, c, m, n, k, stream);
+  const bool want8p = env8p > 0 || (env8p == 0 && act == 0 && !big);
+  // 8-phase: full tiles only, k / 64 >= 3 for its pipeline depth, and at
+  // least 64 tiles (chip fill)
+  if (want8p && m % 256 == 0 && n % 256 == 0 && k % 64 == 0 &&
+      k / 64 >= 3 && tiles >= 64)
+    return VFA_ROUTE_8P;
+  if (!big) return VFA_ROUTE_SMALL;
+  // interior tile columns -> the persistent kernel when K has no ragged
+  // step (n % 8: its 16-B bias/res/out vectors need 8-element row
+  // alignment); the guarded kernel then takes only the ragged last column
+  if (k % BK != 0 || n % 8 != 0) return VFA_ROUTE_BIG_GUARD;
+  return n % 256 == 0 ? VFA_ROUTE_256P : VFA_ROUTE_256P_EDGE;
 }
-
-}  // namespace
-
-extern "C" {
 
 // act: 0 none, 1 relu, 2 quick_gelu, 3 gelu_tanh, 4 leaky_relu(0.1)
 void vfa_linear_act(const void* a, const void* w, const void* bias,

@@ -188,6 +188,19 @@ void vfa_avgpool2d_nhwc(const void* x, void* out, long long n, int c, int ih,
 void vfa_linear_act(const void* a, const void* w, const void* bias,
                     const void* res, void* c, int m, int n, int k, int act,
                     hipStream_t stream);
+// The kernel vfa_linear_act runs for an (m, n, k) problem with activation
+// id act — the function its launchers call (also bound to Python as
+// linear_route, so a test can pin a shape).  *nch: the thin kernel's
+// N-chunk, 0 on every other route.
+enum {
+  VFA_ROUTE_THIN = 0,       // linear_thin_kernel
+  VFA_ROUTE_8P = 1,         // linear8p_kernel
+  VFA_ROUTE_256P = 2,       // linear256p_kernel, every tile
+  VFA_ROUTE_256P_EDGE = 3,  // linear256p_kernel + guarded last tile column
+  VFA_ROUTE_BIG_GUARD = 4,  // 256^2 linear_act_kernel (ragged K or n % 8)
+  VFA_ROUTE_SMALL = 5,      // 128^2 linear_act_kernel
+};
+int vfa_linear_route(int m, int n, int k, int act, int* nch);
 // s = a @ w^T + bias + res (bf16) and, per row of s and 256-column group
 // (tile column), the (mean, M2) of the rounded values: part (M, N/256)
 // float2.  Full tiles only (m % 256 == n % 256 == k % 64 == 0; the binding
