@@ -108,13 +108,14 @@ torch::Tensor layer_norm(torch::Tensor x, torch::Tensor w, torch::Tensor b,
   auto wc = w.contiguous().to(x.scalar_type());
   auto bc = b.contiguous().to(x.scalar_type());
   auto out = torch::empty_like(x);
+  if (x.numel() == 0) return out;
   vfa_layer_norm(x.data_ptr(), wc.data_ptr(), bc.data_ptr(), out.data_ptr(),
                  x.numel() / d, d, (float)eps, dtype_tag(x), current_stream());
   return out;
 }
 
 // (T, P, W) patch embeddings + cls (W) + pos (P+1, W) -> ln_pre'd tokens
-// (T, P+1, W); see clip_embed_ln_kernel
+// (T, P+1, W); see EmbedSrc in layernorm.hip
 torch::Tensor clip_embed_ln(torch::Tensor pe, torch::Tensor cls,
                             torch::Tensor pos, torch::Tensor w,
                             torch::Tensor b, double eps) {
@@ -131,6 +132,7 @@ torch::Tensor clip_embed_ln(torch::Tensor pe, torch::Tensor cls,
   auto wc = w.contiguous().to(pe.scalar_type());
   auto bc = b.contiguous().to(pe.scalar_type());
   auto out = torch::empty({(long)t, p + 1, d}, pe.options());
+  if (out.numel() == 0) return out;
   vfa_clip_embed_ln(pe.data_ptr(), cc.data_ptr(), pc.data_ptr(),
                     wc.data_ptr(), bc.data_ptr(), out.data_ptr(),
                     t * (p + 1), p, d, (float)eps, dtype_tag(pe),
@@ -266,10 +268,12 @@ std::vector<torch::Tensor> layer_norm_residual(torch::Tensor x,
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && res.is_contiguous());
   TORCH_CHECK(x.sizes() == res.sizes());
   const int d = (int)x.size(-1);
+  TORCH_CHECK(w.numel() == d && b.numel() == d, "affine shape mismatch");
   auto wc = w.contiguous().to(x.scalar_type());
   auto bc = b.contiguous().to(x.scalar_type());
   auto y = torch::empty_like(x);
   auto s = torch::empty_like(x);
+  if (x.numel() == 0) return {y, s};
   vfa_layer_norm_residual(x.data_ptr(), res.data_ptr(), wc.data_ptr(),
                           bc.data_ptr(), y.data_ptr(), s.data_ptr(),
                           x.numel() / d, d, (float)eps, dtype_tag(x),

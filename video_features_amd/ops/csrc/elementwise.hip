@@ -20,21 +20,20 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 template <typename T, int VEC, int KIND>  // KIND 0=quick_gelu 1=gelu_tanh
 __global__ void act_kernel(const T* __restrict__ in, T* __restrict__ out,
                            long long n) {
-  using VecT = __attribute__((ext_vector_type(VEC * sizeof(T) / 4))) unsigned;
+  static_assert(VEC * sizeof(T) == 16, "one 16-B vector per thread");
   long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
        i * VEC < n; i += stride) {
     long long base = i * VEC;
     if (base + VEC <= n) {
-      VecT v = *reinterpret_cast<const VecT*>(in + base);
       T tmp[VEC];
-      *reinterpret_cast<VecT*>(tmp) = v;
+      load16(tmp, in + base);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         float x = to_f32<T>(tmp[j]);
         tmp[j] = from_f32<T>(KIND == 0 ? quick_gelu_f(x) : gelu_tanh_f(x));
       }
-      *reinterpret_cast<VecT*>(out + base) = *reinterpret_cast<VecT*>(tmp);
+      store16(out + base, tmp);
     } else {
       for (long long j = base; j < n; ++j) {
         float x = to_f32<T>(in[j]);

@@ -71,6 +71,20 @@ __device__ __forceinline__ __half from_f32<__half>(float v) {
   return __float2half(v);
 }
 
+// One 16-B access for 16 / sizeof(T) elements of T: memory -> register array
+// and back.  `mem` must be 16-B aligned.
+template <typename T>
+__device__ __forceinline__ void load16(T* reg, const T* mem) {
+  using VecT = __attribute__((ext_vector_type(4))) unsigned;
+  *reinterpret_cast<VecT*>(reg) = *reinterpret_cast<const VecT*>(mem);
+}
+
+template <typename T>
+__device__ __forceinline__ void store16(T* mem, const T* reg) {
+  using VecT = __attribute__((ext_vector_type(4))) unsigned;
+  *reinterpret_cast<VecT*>(mem) = *reinterpret_cast<const VecT*>(reg);
+}
+
 // 8 bf16 in one 16-B vector <-> 8 f32 (memory-bound kernels move bf16 as
 // uint4; the f32 -> bf16 direction rounds to nearest even, NaN kept quiet)
 __device__ __forceinline__ void bf16x8_to_f32(const uint4& v, float* f) {
