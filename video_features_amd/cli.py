@@ -7,7 +7,7 @@ from __future__ import annotations
 import argparse
 from typing import List, Optional
 
-from .config import FEATURE_TYPES, Config, sanity_check
+from .config import FEATURE_TYPES, RAFT_CORR_MODES, Config, sanity_check
 from .runtime.dist import run_extraction
 
 
@@ -56,6 +56,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--profile', action='store_true', default=False)
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--weights_path', type=str, default=None)
+    p.add_argument('--raft_corr', choices=RAFT_CORR_MODES, default='allpairs',
+                   help='RAFT correlation: all-pairs volume (quadratic in '
+                        'frame area), on-the-fly lookup (linear), or auto '
+                        '(on the fly once the volume would take a quarter '
+                        'of device memory)')
     return p
 
 

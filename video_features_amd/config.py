@@ -26,6 +26,7 @@ FEATURE_TYPES = [
 
 ON_EXTRACTION_CHOICES = ['print', 'save_numpy', 'save_pickle', 'save_jpg']
 FLOW_TYPES = ['raft', 'pwc', 'flow']
+RAFT_CORR_MODES = ['allpairs', 'onthefly', 'auto']
 
 
 @dataclass
@@ -82,6 +83,9 @@ class Config:
     profile: bool = False          # per-stage (decode/transform/infer/save) timings
     seed: int = 0                  # random-init weight seed (no-network setting)
     weights_path: Optional[str] = None  # optional state_dict file for the model
+    # RAFT correlation: 'allpairs' (volume quadratic in frame area),
+    # 'onthefly' (memory linear in frame area) or 'auto' (by volume size)
+    raft_corr: str = 'allpairs'
 
     # ---- temporal (context) parallelism: shard ONE video's sliding
     # windows across ranks — exact, windows are independent (the flow
@@ -149,3 +153,6 @@ def sanity_check(cfg: Config) -> None:
             raise ValueError(f'unknown streams {sorted(bad)}; choices: rgb, flow')
     if cfg.dtype not in ('auto', 'fp32', 'bf16'):
         raise ValueError(f"dtype must be 'auto'|'fp32'|'bf16', got {cfg.dtype!r}")
+    if cfg.raft_corr not in RAFT_CORR_MODES:
+        raise ValueError(f'raft_corr must be one of {RAFT_CORR_MODES}, '
+                         f'got {cfg.raft_corr!r}')

@@ -77,7 +77,7 @@ class ExtractI3D(BaseExtractor):
             self._maybe_load(flow, 'i3d_flow')
             models['flow'] = flow.to(device, dtype).eval()
             if self.flow_type == 'raft':
-                raft = RAFT()
+                raft = RAFT(corr=self.cfg.raft_corr)
                 self._maybe_load(raft, 'raft')
                 raft = raft.to(device, dtype).eval()
                 if device.type == 'cuda':

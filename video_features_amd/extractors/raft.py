@@ -28,7 +28,7 @@ class ExtractRAFT(BaseExtractor):
         self.resize_smaller = self.cfg.resize_to_smaller_edge
 
     def build_models(self, device: torch.device, dtype: torch.dtype):
-        model = RAFT()
+        model = RAFT(corr=self.cfg.raft_corr)
         if self.cfg.weights_path:
             self.load_weights(model, self.cfg.weights_path)
         return model.to(device=device, dtype=dtype).eval()

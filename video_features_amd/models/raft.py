@@ -11,6 +11,10 @@ MI355X mapping (all decisions measured with rocprofv3, profiles/):
     kernel (``ops.corr_lookup``) with the per-pixel correlation planes
     staged through LDS — the reference runs 4 grid_samples plus window
     tensor construction per iteration;
+  * ``RAFT(corr='onthefly')`` skips the all-pairs volume, whose size is
+    quadratic in the frame area: ``ops.corr_lookup_otf`` computes each
+    lookup's 100 dot products per (pixel, level) from the feature maps
+    (reference AlternateCorrBlock); ``'auto'`` switches by volume size;
   * the SepConvGRU z/r convs are merged into one conv and the gate
     elementwise is fused (``ops.gru_zr`` / ``ops.gru_out``), with the
     conv inputs kept in two persistent (B, 384, H/8, W/8) buffers instead
@@ -31,6 +35,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import ops
+from ..config import RAFT_CORR_MODES
 
 
 # --------------------------------------------------------------- encoders
@@ -154,6 +159,48 @@ class CorrPyramid:
                                self.radius, nhwc, out_dtype)
 
 
+class CorrOnTheFly:
+    """The same lookup without the all-pairs volume (reference
+    AlternateCorrBlock, corr.py:63-91): holds fmap1 and the avg-pooled
+    levels of fmap2 in f32, pixel-major, and ``ops.corr_lookup_otf``
+    computes the 100 dot products per (pixel, level) a lookup needs.  Memory
+    is linear in the frame area — ``nbytes`` — where CorrPyramid's is
+    quadratic."""
+
+    def __init__(self, fmap1: torch.Tensor, fmap2: torch.Tensor,
+                 num_levels: int = 4, radius: int = 4):
+        self.num_levels = num_levels
+        self.radius = radius
+        b, d, h, w = fmap1.shape
+        self.shape = (b, h, w)
+        self.f1 = fmap1.float().permute(0, 2, 3, 1).contiguous()
+        f2 = fmap2.float()
+        self.f2_levels: List[torch.Tensor] = []
+        for lvl in range(num_levels):
+            if lvl:
+                f2 = F.avg_pool2d(f2, 2, 2)
+            self.f2_levels.append(f2.permute(0, 2, 3, 1).contiguous())
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size()
+                   for t in [self.f1, *self.f2_levels])
+
+    def __call__(self, coords: torch.Tensor, nhwc: bool = False,
+                 out_dtype: torch.dtype = None) -> torch.Tensor:
+        return ops.corr_lookup_otf(self.f1, self.f2_levels,
+                                   coords.contiguous(), self.radius, nhwc,
+                                   out_dtype)
+
+
+def corr_mode_for(b: int, h8: int, w8: int, total_bytes: int) -> str:
+    """'auto': on the fly once the all-pairs pyramid —
+    4 * (1 + 1/4 + 1/16 + 1/64) * b * (h8 * w8)^2 bytes — would take more
+    than a quarter of the device's memory."""
+    return ('onthefly' if 5.3125 * b * (h8 * w8) ** 2 > total_bytes / 4
+            else 'allpairs')
+
+
 # ----------------------------------------------------------------- update
 class FlowHead(nn.Module):
     def __init__(self, in_dim: int = 128, hidden: int = 256):
@@ -271,10 +318,14 @@ class BasicUpdateBlock(nn.Module):
 # ------------------------------------------------------------------- RAFT
 class RAFT(nn.Module):
     def __init__(self, hidden_dim: int = 128, context_dim: int = 128,
-                 iters: int = 20):
+                 iters: int = 20, corr: str = 'allpairs'):
         super().__init__()
+        if corr not in RAFT_CORR_MODES:
+            raise ValueError(
+                f'corr must be one of {RAFT_CORR_MODES}, got {corr!r}')
         self.hdim, self.cdim = hidden_dim, context_dim
         self.iters = iters
+        self.corr = corr
         self.nhwc = False
         self.fnet = BasicEncoder(256, 'instance')
         self.cnet = BasicEncoder(hidden_dim + context_dim, 'batch')
@@ -292,6 +343,19 @@ class RAFT(nn.Module):
                                 indexing='ij')
         return torch.stack([xx, yy])[None].expand(b, -1, -1, -1).contiguous()
 
+    def _corr_class(self, fmap1: torch.Tensor):
+        """CorrPyramid or CorrOnTheFly for this forward; 'auto' asks
+        ``corr_mode_for`` with the device's total memory (all-pairs on the
+        CPU) — a host-side property read, no sync."""
+        mode = self.corr
+        if mode == 'auto':
+            mode = 'allpairs'
+            if fmap1.is_cuda:
+                b, _, h8, w8 = fmap1.shape
+                mode = corr_mode_for(b, h8, w8, torch.cuda.get_device_properties(
+                    fmap1.device).total_memory)
+        return CorrOnTheFly if mode == 'onthefly' else CorrPyramid
+
     def forward(self, image1: torch.Tensor, image2: torch.Tensor,
                 iters: int = None, test_mode: bool = True):
         """uint8-range (B, 3, H, W) pairs (H, W divisible by 8) → (B, 2, H, W)
@@ -307,7 +371,7 @@ class RAFT(nn.Module):
         # one batched encoder pass over both images (fewer, larger GEMMs)
         fmap = self.fnet(torch.cat([image1, image2]))
         fmap1, fmap2 = fmap[:b], fmap[b:]
-        corr_fn = CorrPyramid(fmap1.float(), fmap2.float())
+        corr_fn = self._corr_class(fmap1)(fmap1.float(), fmap2.float())
         cnet = self.cnet(image1)
         net, inp = torch.split(cnet, [self.hdim, self.cdim], dim=1)
         inp = F.relu(inp)

@@ -425,6 +425,76 @@ def corr_lookup(pyramid, coords: torch.Tensor, radius: int = 4,
         else res.contiguous()
 
 
+def _corr_otf_axis(c: torch.Tensor, lvl: int, n: int):
+    """One axis of one level: (integer origin of the 10-point grid, shared
+    fractional part) of pixel coordinate ``c / 2**lvl`` on a level ``n``
+    points long.  floor is clamped to [-16, n + 16] (a window wholly outside
+    either way), so huge or non-finite coordinates index nothing."""
+    s = c / (2 ** lvl)
+    f = torch.floor(s)
+    fc = torch.nan_to_num(f, nan=-16.0).clamp(-16.0, n + 16.0)
+    a = torch.where(f == fc, s - f, torch.zeros_like(s))
+    return fc.long() - 4, a
+
+
+def corr_lookup_otf(f1: torch.Tensor, f2_levels, coords: torch.Tensor,
+                    radius: int = 4, nhwc: bool = False,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """RAFT correlation lookup computed on the fly from the features: what
+    ``corr_lookup`` returns for the all-pairs pyramid of the same feature
+    maps, without building that pyramid (reference AlternateCorrBlock,
+    models/raft/raft_src/corr.py:63-91).
+
+    ``f1``: (B, H, W, D) fp32, pixel-major; ``f2_levels``: up to 4 levels
+    (B, h_l, w_l, D) fp32, the second feature map avg-pooled l times;
+    ``coords``: (B, 2, H, W) fp32 pixel coords at level 0.  Returns
+    (B, L*(2r+1)^2, H, W), tap t = i*(2r+1)+j offsetting X by i-r and Y by
+    j-r.  Average pooling and the dot product are linear, so level l of the
+    pooled volume is f1 . f2_l; the (2r+1)^2 taps of a pixel share one
+    fractional part and read the (2r+2)^2 integer grid around
+    floor(coords / 2^l): that many dot products, then four-term blends.
+
+    GPU tensors with radius 4, D % 32 == 0 and D <= 256 run the HIP kernel
+    (``corr_otf``: one wave per query pixel, one dispatch for all levels).
+    CPU tensors and other shapes run the torch composition below, which
+    indexes in pixel units (a level 1 wide or 1 high is sampled where the
+    mathematics puts it)."""
+    if out_dtype is None:
+        out_dtype = coords.dtype
+    b, h, w, d = f1.shape
+    if (_use_hip(coords) and radius == 4 and d % 32 == 0 and d <= 256
+            and len(f2_levels) <= 4):
+        return _ext.corr_lookup_otf(f1, list(f2_levels),
+                                    coords.float().contiguous(), nhwc,
+                                    out_dtype)
+    n = 2 * radius + 2               # grid points per axis
+    ar = torch.arange(n, device=coords.device)
+    cx, cy = coords[:, 0].float(), coords[:, 1].float()     # (B, H, W)
+    bi = torch.arange(b, device=coords.device).view(b, 1, 1, 1, 1)
+    out = []
+    for lvl, f2 in enumerate(f2_levels):
+        hl, wl = f2.shape[1:3]
+        x0, ax = _corr_otf_axis(cx, lvl, wl)
+        y0, ay = _corr_otf_axis(cy, lvl, hl)
+        if radius != 4:
+            x0, y0 = x0 + 4 - radius, y0 + 4 - radius
+        x = (x0[..., None] + ar)[..., :, None]              # (B, H, W, n, 1)
+        y = (y0[..., None] + ar)[..., None, :]              # (B, H, W, 1, n)
+        ok = (x >= 0) & (x < wl) & (y >= 0) & (y < hl)
+        g = f2[bi, y.clamp(0, hl - 1), x.clamp(0, wl - 1)]  # (B,H,W,n,n,D)
+        c = torch.einsum('bhwd,bhwijd->bhwij', f1, g) / math.sqrt(d)
+        c = c * ok.to(c.dtype)
+        ax, ay = ax[..., None, None], ay[..., None, None]
+        v = ((1 - ax) * (1 - ay) * c[..., :-1, :-1]
+             + ax * (1 - ay) * c[..., 1:, :-1]
+             + (1 - ax) * ay * c[..., :-1, 1:]
+             + ax * ay * c[..., 1:, 1:])
+        out.append(v.reshape(b, h, w, -1))
+    res = torch.cat(out, dim=-1).permute(0, 3, 1, 2).to(out_dtype)
+    return res.contiguous(memory_format=torch.channels_last) if nhwc \
+        else res.contiguous()
+
+
 def convex_upsample(flow: torch.Tensor, mask: torch.Tensor,
                     nhwc: bool = False) -> torch.Tensor:
     """RAFT convex-combination 8x flow upsample (reference raft.py:100-111).

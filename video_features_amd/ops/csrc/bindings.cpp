@@ -386,6 +386,58 @@ torch::Tensor corr_lookup(std::vector<torch::Tensor> pyramid,
   return out;
 }
 
+torch::Tensor corr_lookup_otf(torch::Tensor f1,
+                              std::vector<torch::Tensor> f2_levels,
+                              torch::Tensor coords, bool nhwc,
+                              torch::ScalarType out_dtype) {
+  // f1 (B, H, W, D) and f2_levels[l] (B, h_l, w_l, D): fp32, pixel-major;
+  // coords (B, 2, H, W) fp32 pixel units at level 0.  Returns what
+  // corr_lookup returns for the all-pairs pyramid of the same features.
+  const int levels = (int)f2_levels.size();
+  TORCH_CHECK(levels >= 1 && levels <= 4, "1..4 feature levels");
+  const int tag = dtype_tag(out_dtype);   // raises before anything launches
+  TORCH_CHECK(f1.is_cuda() && f1.dim() == 4 && f1.is_contiguous() &&
+              f1.scalar_type() == torch::kFloat32,
+              "f1 must be a contiguous f32 (B, H, W, D) GPU tensor");
+  const long long b = f1.size(0);
+  const int h = (int)f1.size(1), w = (int)f1.size(2);
+  const int d = (int)f1.size(3);
+  TORCH_CHECK(d % 32 == 0 && d >= 32 && d <= 256,
+              "D must be a multiple of 32, at most 256");
+  TORCH_CHECK(coords.is_cuda() && coords.dim() == 4 &&
+              coords.is_contiguous() &&
+              coords.scalar_type() == torch::kFloat32 &&
+              coords.size(0) == b && coords.size(1) == 2 &&
+              coords.size(2) == h && coords.size(3) == w,
+              "coords must be a contiguous f32 (B, 2, H, W) GPU tensor");
+  TORCH_CHECK((long long)h * w < (1LL << 31), "frame too large");
+  CorrPyramid lv;
+  for (int l = 0; l < levels; ++l) {
+    auto& t = f2_levels[l];
+    TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.is_contiguous() &&
+                t.scalar_type() == torch::kFloat32 &&
+                t.get_device() == f1.get_device(),
+                "f2 levels must be contiguous f32 GPU tensors");
+    TORCH_CHECK(t.size(0) == b && t.size(3) == d && t.size(1) >= 1 &&
+                t.size(2) >= 1 && t.size(1) <= h && t.size(2) <= w,
+                "f2 level ", l, " must be (B, 1..H, 1..W, D)");
+    lv.hs[l] = (int)t.size(1);
+    lv.ws[l] = (int)t.size(2);
+    lv.lvl[l] = t.data_ptr();
+  }
+  for (int l = levels; l < 4; ++l) {
+    lv.hs[l] = lv.ws[l] = 1;
+    lv.lvl[l] = lv.lvl[levels - 1];
+  }
+  const int ctot = levels * 81;
+  auto opts = coords.options().dtype(out_dtype);
+  auto out = nhwc ? empty_nhwc(b, ctot, h, w, opts)
+                  : torch::empty({b, ctot, h, w}, opts);
+  vfa_corr_otf(f1.data_ptr(), lv, coords.data_ptr(), out.data_ptr(), levels,
+               b * h * w, h * w, d, nhwc ? 1 : 0, tag, current_stream());
+  return out;
+}
+
 torch::Tensor convex_upsample(torch::Tensor flow, torch::Tensor mask,
                               bool nhwc) {
   TORCH_CHECK(flow.is_cuda() && flow.dim() == 4 && flow.size(1) == 2);
@@ -895,6 +947,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_chw_norm", &u8_chw_norm);
   m.def("patchify", &patchify);
   m.def("corr_lookup", &corr_lookup);
+  m.def("corr_lookup_otf", &corr_lookup_otf);
   m.def("convex_upsample", &convex_upsample);
   m.def("gru_zr", &gru_zr);
   m.def("gru_out", &gru_out);

@@ -13,6 +13,9 @@
 //    a whole (h_l, w_l) plane per level; total ~4.2 KB for 28x28 feature
 //    maps, far under the 160 KB LDS/CU).  Zero-padding bilinear semantics
 //    identical to torch grid_sample(align_corners=True, padding='zeros').
+//  - vfa_corr_otf: the same lookup computed from the feature maps, for
+//    frames whose all-pairs volume (quadratic in frame area) does not fit:
+//    100 dot products + 81 blends per (pixel, level), memory linear in area.
 //  - vfa_convex_upsample: softmax(0.25*mask) convex combination of the 3x3
 //    neighborhood of 8*flow, one thread per upsampled pixel.
 //  - vfa_gru_zr / vfa_gru_out: the SepConvGRU gate elementwise, fused so the
@@ -148,6 +151,128 @@ __global__ void corr_lookup_gmem_kernel(const float* __restrict__ l0,
     out[oi] = from_f32<T>(v);
   }
   (void)loffs;
+}
+
+// ------------------------------------------------- on-the-fly corr lookup
+// The same lookup without the all-pairs volume: avg-pooling and the dot
+// product are linear, so level l of the pooled volume is f1 . avgpool_l(f2),
+// and the 81 taps of a (pixel, level) sample the 10x10 integer grid around
+// floor(coords / 2^l) with ONE shared fractional part.  Per (pixel, level):
+// 100 dots C[i][j] = f1[p] . f2_l[y0 + j][x0 + i] / sqrt(D) (0 outside the
+// level), then 81 four-term blends of C; tap t = i*9+j as above.
+//
+// f1 (B, H, W, D), f2 level l (B, h_l, w_l, D): f32, pixel-major.  One wave
+// per query pixel, OTF_WPB waves per block, no workgroup barrier.  Lane =
+// (grid-point group g = lane >> 3, 16-B segment sg = lane & 7); chunk k of a
+// lane is channels [32k + 4sg, 32k + 4sg + 4), so the 8 lanes of a group
+// read 128 contiguous bytes per load and f1[p] stays in registers (D <= 256:
+// 8 chunks).  The levels' grids are one list of levels*100 points; a round
+// takes 8 of them, OTF_RPI rounds have all their loads issued before the
+// first use.  Loads of points outside their level are predicated off.
+// Partial dots are summed over the 8 segment lanes, C goes to a wave-private
+// LDS tile, and after a wave_barrier the 64 lanes form the levels*81 blends.
+constexpr int OTF_WPB = 4;   // waves (query pixels) per block
+constexpr int OTF_RPI = 2;   // rounds in flight
+constexpr int OTF_NCH = 8;   // 32-channel chunks a lane can hold (D <= 256)
+
+// integer origin (leftmost grid column / top row) and fractional part of
+// one axis at one level.  floor(s) is clamped before the int conversion, so
+// a huge or non-finite coordinate gives a window wholly outside the level
+// (and a zero fraction) instead of an out-of-range index.
+__device__ __forceinline__ void otf_origin(float c, float inv, int n, int& i0,
+                                           float& a) {
+  const float s = c * inv;
+  const float f = floorf(s);
+  const float fc = fminf(fmaxf(f, -16.f), (float)n + 16.f);
+  i0 = (int)fc - 4;
+  a = (f == fc) ? s - f : 0.f;
+}
+
+template <typename T, bool NHWC>
+__global__ __launch_bounds__(64 * OTF_WPB) void corr_otf_kernel(
+    const float* __restrict__ f1, const float* __restrict__ l0,
+    const float* __restrict__ l1, const float* __restrict__ l2,
+    const float* __restrict__ l3, const float* __restrict__ coords,
+    T* __restrict__ out, int levels, int4 hs, int4 ws, long long npix, int hw,
+    int d, float rsqrt_d) {
+  __shared__ float tiles[OTF_WPB][400];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int g = lane >> 3, sg = lane & 7;
+  const long long pix = (long long)blockIdx.x * OTF_WPB + wv;
+  if (pix >= npix) return;
+  float* tile = tiles[wv];
+  const long long b = pix / hw;
+  const int p = (int)(pix % hw);
+  const float cx = coords[(b * 2 + 0) * hw + p];
+  const float cy = coords[(b * 2 + 1) * hw + p];
+  const int nch = d >> 5;
+
+  // this lane's share of f1[p]
+  float q[OTF_NCH][4];
+#pragma unroll
+  for (int k = 0; k < OTF_NCH; ++k) {
+    q[k][0] = q[k][1] = q[k][2] = q[k][3] = 0.f;
+    if (k < nch) load16(q[k], f1 + pix * d + k * 32 + sg * 4);
+  }
+
+  const int npts = levels * 100;
+  for (int r0 = 0; r0 < npts; r0 += 8 * OTF_RPI) {
+    float v[OTF_RPI][OTF_NCH][4];
+#pragma unroll
+    for (int r = 0; r < OTF_RPI; ++r) {
+      const int gp = r0 + 8 * r + g;
+      const int l = gp / 100, ij = gp % 100;
+      const int h = l == 0 ? hs.x : l == 1 ? hs.y : l == 2 ? hs.z : hs.w;
+      const int w = l == 0 ? ws.x : l == 1 ? ws.y : l == 2 ? ws.z : ws.w;
+      const float* fl = l == 0 ? l0 : l == 1 ? l1 : l == 2 ? l2 : l3;
+      const float inv = 1.0f / (float)(1 << l);
+      int x0, y0;
+      float ax, ay;
+      otf_origin(cx, inv, w, x0, ax);
+      otf_origin(cy, inv, h, y0, ay);
+      const int x = x0 + ij / 10, y = y0 + ij % 10;
+      const bool ok = gp < npts && x >= 0 && x < w && y >= 0 && y < h;
+      const float* src = fl + ((b * h + y) * w + x) * d + sg * 4;
+#pragma unroll
+      for (int k = 0; k < OTF_NCH; ++k) {
+        v[r][k][0] = v[r][k][1] = v[r][k][2] = v[r][k][3] = 0.f;
+        if (k < nch && ok) load16(v[r][k], src + k * 32);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < OTF_RPI; ++r) {
+      float dot = 0.f;
+#pragma unroll
+      for (int k = 0; k < OTF_NCH; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dot += q[k][e] * v[r][k][e];
+#pragma unroll
+      for (int off = 1; off < 8; off <<= 1) dot += __shfl_xor(dot, off, 64);
+      const int gp = r0 + 8 * r + g;
+      if (sg == 0 && gp < npts) tile[gp] = dot * rsqrt_d;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // the tile is this wave's own
+
+  const int ctot = levels * 81;
+  for (int c = lane; c < ctot; c += 64) {
+    const int l = c / 81, t = c % 81;
+    const int ix = t / 9, iy = t % 9;
+    const int h = l == 0 ? hs.x : l == 1 ? hs.y : l == 2 ? hs.z : hs.w;
+    const int w = l == 0 ? ws.x : l == 1 ? ws.y : l == 2 ? ws.z : ws.w;
+    const float inv = 1.0f / (float)(1 << l);
+    int x0, y0;
+    float ax, ay;
+    otf_origin(cx, inv, w, x0, ax);
+    otf_origin(cy, inv, h, y0, ay);
+    const float* cp = tile + l * 100 + ix * 10 + iy;
+    const float val = (1 - ax) * (1 - ay) * cp[0] + ax * (1 - ay) * cp[10] +
+                      (1 - ax) * ay * cp[1] + ax * ay * cp[11];
+    const long long oi = NHWC ? (pix * ctot + c)
+                              : ((b * ctot + c) * hw + p);
+    out[oi] = from_f32<T>(val);
+  }
 }
 
 // -------------------------------------------------------- convex upsample
@@ -304,6 +429,27 @@ void vfa_corr_lookup(const CorrPyramid& pyr, const void* coords, void* out,
                            dim3(256), 0, stream, l0, l1, l2, l3, xy, (T*)out,
                            levels, hs, ws, npix, hw);
       }
+    });
+  });
+}
+
+void vfa_corr_otf(const void* f1, const CorrPyramid& f2, const void* coords,
+                  void* out, int levels, long long npix, int hw, int d,
+                  int nhwc, int dtype, hipStream_t stream) {
+  if (npix <= 0) return;
+  const int4 hs = {f2.hs[0], f2.hs[1], f2.hs[2], f2.hs[3]};
+  const int4 ws = {f2.ws[0], f2.ws[1], f2.ws[2], f2.ws[3]};
+  const dim3 grid((unsigned)((npix + OTF_WPB - 1) / OTF_WPB));
+  const float rsqrt_d = 1.0f / sqrtf((float)d);
+  dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_bool(nhwc, [&](auto cl) {
+      hipLaunchKernelGGL((corr_otf_kernel<T, decltype(cl)::value>), grid,
+                         dim3(64 * OTF_WPB), 0, stream, (const float*)f1,
+                         (const float*)f2.lvl[0], (const float*)f2.lvl[1],
+                         (const float*)f2.lvl[2], (const float*)f2.lvl[3],
+                         (const float*)coords, (T*)out, levels, hs, ws, npix,
+                         hw, d, rsqrt_d);
     });
   });
 }

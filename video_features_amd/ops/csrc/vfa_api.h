@@ -31,7 +31,8 @@ struct ConvAddr {
 };
 
 // RAFT correlation pyramid: level l is (npix, 1, hs[l], ws[l]) f32; unused
-// levels repeat the last pointer with hs = ws = 1
+// levels repeat the last pointer with hs = ws = 1.  vfa_corr_otf passes the
+// pooled feature levels (B, hs[l], ws[l], d) in the same struct.
 struct CorrPyramid {
   const void* lvl[4];
   int hs[4], ws[4];
@@ -152,6 +153,13 @@ void vfa_patchify(const void* in, void* out, long long t, int c, int h, int w,
 void vfa_corr_lookup(const CorrPyramid& pyr, const void* coords, void* out,
                      int levels, long long npix, int hw, int lds_floats,
                      int nhwc, int dtype, hipStream_t stream);
+// The same lookup computed from the features (no all-pairs volume): f1
+// (B, H, W, d) f32 and f2.lvl[l] (B, hs[l], ws[l], d) f32, the avg-pooled
+// second feature map, both pixel-major; d % 32 == 0, d <= 256, every level
+// at least 1x1; coords / out / hw / npix as above
+void vfa_corr_otf(const void* f1, const CorrPyramid& f2, const void* coords,
+                  void* out, int levels, long long npix, int hw, int d,
+                  int nhwc, int dtype, hipStream_t stream);
 // flow (b, 2, h, w), mask (b, 576, h, w) -> out (b, 2, 8h, 8w) contiguous
 void vfa_convex_upsample(const void* flow, const void* mask, void* out, int b,
                          int h, int w, int nhwc, int dtype,
