@@ -9,7 +9,9 @@ A row may carry a sixth field, the mode:
   ln_act     ops.linear_ln_act on un-normalised rows with a folded weight
              (torch: F.linear on the already normalised rows)
 After the rows come the LayerNorm-fold chains (CHAINS): what a ViT block
-runs today against the folded pair, each chain replayed from one graph.
+runs today against the folded pair, each chain replayed from one graph, and
+ops.instance_norm alone at the calls of RAFT's feature net (VFA_GEMM_ONLY=
+instance_norm selects them).
 
 VFA_GEMM_GRAPH=1 times every row from a captured graph (kernel time without
 launch gaps); the chains always do."""
@@ -235,3 +237,52 @@ for label, m, wd, k1, n2, act2, gemm2 in CHAINS:
         print(f'    {name:<22} {timeit_graph(fn) * 1e6:7.1f} us', flush=True)
     d = (folded()[0].float() - today()[0].float()).abs().max().item()
     print(f'    max |folded - today| {d:.3e}', flush=True)
+
+
+# ------------------------------------------------------------- InstanceNorm
+# ops.instance_norm alone, replayed from a graph like the chains, at the
+# shapes, layout and ReLU flags with which the RAFT feature net calls it in
+# ``bench.py --model i3d_raft`` (16 clips x 64 frame pairs, both images in
+# one batch: 2048 frames of 224 x 224, bf16 channels_last).  The calls are
+# read off the model with forward hooks on a 2-frame batch and printed once.
+# Two inputs per shape: planes with mean 0, whose variance the kernel takes
+# from sumsq/n - mean^2, and planes with mean 2 sigma, which it sweeps once
+# more for the variance about the mean.  VFA_NORM_FRAMES overrides the 2048.
+def fnet_norm_calls():
+    """{(C, H, W, nhwc, relu): count} of one feature-net forward."""
+    from video_features_amd.models.raft import (BasicEncoder,
+                                                FusedInstanceNorm2d)
+    cl = torch.channels_last
+    net = BasicEncoder(256, 'instance').to(dev, torch.bfloat16) \
+        .to(memory_format=cl).eval()
+    calls = {}
+
+    def hook(mod, inp, out):
+        x = inp[0]
+        key = (*x.shape[1:], not x.is_contiguous(), mod.fuses_relu)
+        calls[key] = calls.get(key, 0) + 1
+    for mod in net.modules():
+        if isinstance(mod, FusedInstanceNorm2d):
+            mod.register_forward_hook(hook)
+    with torch.no_grad():
+        net(torch.randn(2, 3, 224, 224, device=dev).to(torch.bfloat16)
+            .contiguous(memory_format=cl))
+    return calls
+
+
+if not ONLY or ONLY in 'instance_norm':
+    frames = int(os.environ.get('VFA_NORM_FRAMES', '2048'))
+    for (c, h, w, nhwc, relu), count in fnet_norm_calls().items():
+        label = (f'instance_norm ({frames}, {c}, {h}, {w}) '
+                 f'{"nhwc" if nhwc else "nchw"} relu={int(relu)} '
+                 f'x{count} per forward')
+        torch.manual_seed(0)
+        x = torch.randn(frames, c, h, w, device=dev).to(torch.bfloat16)
+        if nhwc:
+            x = x.contiguous(memory_format=torch.channels_last)
+        for name, xin in (('mean 0', x), ('mean 2 sigma', x + 2)):
+            runs = [timeit_graph(lambda: ops.instance_norm(
+                xin, relu=relu, nhwc=nhwc), iters=20) * 1e6 for _ in range(3)]
+            print(f'{label}, {name}: '
+                  + ' '.join(f'{t:8.1f}' for t in runs) + ' us', flush=True)
+        del x, xin

@@ -480,6 +480,7 @@ void gru_out(torch::Tensor q, torch::Tensor z, torch::Tensor hx, bool nhwc) {
 torch::Tensor instance_norm2d(torch::Tensor x, double eps, bool relu,
                               bool nhwc) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4);
+  if (x.numel() == 0) return torch::empty_like(x);  // no layout to speak of
   check_layout(x, nhwc);
   auto out = torch::empty_like(x);
   vfa_instance_norm2d(x.data_ptr(), out.data_ptr(), (int)x.size(0),

@@ -16,34 +16,72 @@
 
 namespace {
 
+// Mean and variance of a plane of n values, for both layouts, from the f32
+// sums of x - k and (x - k)^2 about the plane's first value k.  With m the
+// mean of x - k, s2/n - m^2 loses log2(1 + m^2/var) bits to cancellation; k
+// is a sample of the plane, so that is a bit or two whatever offset the
+// plane carries, and a constant plane gives exactly 0.  It stands where at
+// most 4 bits go (m^2 <= 15 var, which also makes it non-negative).  A first
+// value further out (an outlier) sets `centre`: the kernel then sweeps the
+// plane once more for the sums of x - mean and (x - mean)^2 and hands them
+// to centred(): s1 takes the rounding of the first sum out of the mean, and
+// m2/n, the spread about the old mean, is at least 0 and above the variance
+// by (s1/n)^2, the square of a rounding error.
+struct PlaneStats {
+  float mean, var;
+  bool centre;
+  __device__ PlaneStats(float k, float sum, float sumsq, int n) {
+    const float m = sum / n;
+    mean = k + m;
+    var = sumsq / n - m * m;
+    centre = !(m * m <= 15.f * var);
+  }
+  __device__ void centred(float s1, float m2, int n) {
+    mean += s1 / n;
+    var = m2 / n;
+  }
+  __device__ float rstd(float eps) const { return rsqrtf(var + eps); }
+};
+
 template <typename T, bool RELU>
 __global__ void in2d_nchw_kernel(const T* __restrict__ x, T* __restrict__ out,
                                  int hw, float eps) {
   const long long base = (long long)blockIdx.x * hw;
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const int nwave = blockDim.x / 64;
+  __shared__ float red[2][16];
+  // a and b summed over the block, in every thread; a barrier has to
+  // separate two calls
+  auto block_sum = [&](float& a, float& b) {
+    a = wave_allreduce_sum(a);
+    b = wave_allreduce_sum(b);
+    if (lane == 0) { red[0][wave] = a; red[1][wave] = b; }
+    __syncthreads();
+    a = wave_allreduce_sum(lane < nwave ? red[0][lane] : 0.f);
+    b = wave_allreduce_sum(lane < nwave ? red[1][lane] : 0.f);
+  };
+
+  const float k = to_f32<T>(x[base]);
   float s = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < hw; i += blockDim.x) {
-    const float v = to_f32<T>(x[base + i]);
+    const float v = to_f32<T>(x[base + i]) - k;
     s += v;
     s2 += v * v;
   }
-  __shared__ float red[2][16];
-  s = wave_allreduce_sum(s);
-  s2 = wave_allreduce_sum(s2);
-  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  const int nwave = blockDim.x / 64;
-  if (lane == 0) { red[0][wave] = s; red[1][wave] = s2; }
-  __syncthreads();
-  if (wave == 0) {
-    s = lane < nwave ? red[0][lane] : 0.f;
-    s2 = lane < nwave ? red[1][lane] : 0.f;
-    s = wave_allreduce_sum(s);
-    s2 = wave_allreduce_sum(s2);
-    if (lane == 0) { red[0][0] = s; red[1][0] = s2; }
+  block_sum(s, s2);
+  PlaneStats st(k, s, s2, hw);
+  if (__builtin_expect(st.centre, 0)) {  // block-uniform
+    float s1 = 0.f, m2 = 0.f;
+    for (int i = threadIdx.x; i < hw; i += blockDim.x) {
+      const float d = to_f32<T>(x[base + i]) - st.mean;
+      s1 += d;
+      m2 += d * d;
+    }
+    __syncthreads();
+    block_sum(s1, m2);
+    st.centred(s1, m2, hw);
   }
-  __syncthreads();
-  const float mean = red[0][0] / hw;
-  const float var = red[1][0] / hw - mean * mean;
-  const float rstd = rsqrtf(var + eps);
+  const float mean = st.mean, rstd = st.rstd(eps);
   for (int i = threadIdx.x; i < hw; i += blockDim.x) {
     float v = (to_f32<T>(x[base + i]) - mean) * rstd;
     if (RELU) v = fmaxf(v, 0.f);
@@ -59,32 +97,48 @@ __global__ void in2d_nhwc_kernel(const T* __restrict__ x, T* __restrict__ out,
   const int ch = blockIdx.x * 64 + threadIdx.x;  // channel
   const int row = threadIdx.y;
   const long long base = (long long)blockIdx.y * hw * c;
-  float s = 0.f, s2 = 0.f;
+  __shared__ float red[2][ROWS][64];
+  // a and b summed over the ROWS sub-rows of each lane, in every sub-row;
+  // a barrier has to separate two calls
+  auto column_sum = [&](float& a, float& b) {
+    red[0][row][threadIdx.x] = a;
+    red[1][row][threadIdx.x] = b;
+    __syncthreads();
+    a = red[0][0][threadIdx.x];
+    b = red[1][0][threadIdx.x];
+#pragma unroll
+    for (int r = 1; r < ROWS; ++r) {
+      a += red[0][r][threadIdx.x];
+      b += red[1][r][threadIdx.x];
+    }
+  };
+
+  float k = 0.f, s = 0.f, s2 = 0.f;
   if (ch < c) {
+    k = to_f32<T>(x[base + ch]);
     for (int p = row; p < hw; p += ROWS) {
-      const float v = to_f32<T>(x[base + (long long)p * c + ch]);
+      const float v = to_f32<T>(x[base + (long long)p * c + ch]) - k;
       s += v;
       s2 += v * v;
     }
   }
-  // reduce across the ROWS sub-rows for each lane
-  __shared__ float red[2][ROWS][64];
-  red[0][row][threadIdx.x] = s;
-  red[1][row][threadIdx.x] = s2;
-  __syncthreads();
-  if (row == 0) {
-#pragma unroll
-    for (int r = 1; r < ROWS; ++r) {
-      s += red[0][r][threadIdx.x];
-      s2 += red[1][r][threadIdx.x];
+  column_sum(s, s2);
+  PlaneStats st(k, s, s2, hw);
+  const bool centre = ch < c && st.centre;  // the same in a lane's sub-rows
+  // some channel of this block; also the barrier between the column_sums
+  if (__builtin_expect(__syncthreads_or(centre), 0)) {
+    float s1 = 0.f, m2 = 0.f;
+    if (centre) {
+      for (int p = row; p < hw; p += ROWS) {
+        const float d = to_f32<T>(x[base + (long long)p * c + ch]) - st.mean;
+        s1 += d;
+        m2 += d * d;
+      }
     }
-    red[0][0][threadIdx.x] = s;
-    red[1][0][threadIdx.x] = s2;
+    column_sum(s1, m2);
+    if (centre) st.centred(s1, m2, hw);
   }
-  __syncthreads();
-  const float mean = red[0][0][threadIdx.x] / hw;
-  const float var = red[1][0][threadIdx.x] / hw - mean * mean;
-  const float rstd = rsqrtf(var + eps);
+  const float mean = st.mean, rstd = st.rstd(eps);
   if (ch < c) {
     for (int p = row; p < hw; p += ROWS) {
       const long long i = base + (long long)p * c + ch;

@@ -1,7 +1,9 @@
 // Fused LayerNorm forward for gfx950: one two-pass row kernel for
 // layer_norm, layer_norm_residual and clip_embed_ln.  Pass 1 accumulates
 // sum / sumsq in f32 over 16-B vectors plus a scalar tail, one reduction
-// gives mean and rstd, pass 2 normalises with the affine and rounds once.
+// gives mean and rstd (row_stats; a row whose mean exceeds its spread gets
+// its variance from a sweep of (x - mean)^2 instead), pass 2 normalises with
+// the affine and rounds once.
 // Memory-bound: the target is HBM BW.  Two template parameters:
 //   Src    where a row element comes from (PlainSrc, ResidualSrc, EmbedSrc)
 //   BLOCK  how wide the reduction is: 0 = one wave per row, 4 rows per
@@ -16,9 +18,11 @@ namespace {
 // as f32.  For the 16-B vector i: load<PASS>(i, t) fills up to two register
 // vectors, value<PASS>(t, j) is its element j, keep(i, t) follows the last
 // value of pass 1.  at<PASS>(i) is element i of the scalar tail.  PASS 1 feeds
-// the statistics, PASS 2 the normalisation.  Values are handed over one by
-// one: returned as a float array they make the compiler pair the f16
-// conversions another way, which moves f16 results by a last bit.
+// the statistics, PASS 2 the normalisation; PASS 0 yields the values of pass
+// 1 once more and writes nothing (row_stats' second sweep).  Values are
+// handed over one by one: returned as a float array they make the compiler
+// pair the f16 conversions another way, which moves f16 results by a last
+// bit.
 
 // layer_norm: x[row, i]
 template <typename T>
@@ -41,9 +45,9 @@ struct PlainSrc {
 };
 
 // layer_norm_residual: s = x + res is written once, rounded, in pass 1 and
-// read back in pass 2, so y is the LayerNorm of the stored s (removes the
-// separate add kernel + one full re-read).  Each thread re-reads only what
-// it wrote itself.
+// read back in pass 2, so y is the stored s normalised with the mean and
+// variance of the f32 sums (removes the separate add kernel + one full
+// re-read).  Each thread re-reads only what it wrote itself.
 template <typename T>
 struct ResidualSrc {
   using type = T;
@@ -64,7 +68,7 @@ struct ResidualSrc {
   template <int PASS> __device__ float value(T (*t)[VEC], int j) const {
     if constexpr (PASS == 2) return to_f32<T>(t[0][j]);
     const float v = to_f32<T>(t[0][j]) + to_f32<T>(t[1][j]);
-    t[0][j] = from_f32<T>(v);
+    if constexpr (PASS == 1) t[0][j] = from_f32<T>(v);
     return v;
   }
   __device__ void keep(int i, T (*t)[VEC]) const {
@@ -73,7 +77,7 @@ struct ResidualSrc {
   template <int PASS> __device__ float at(int i) const {
     if constexpr (PASS == 2) return to_f32<T>(s[i]);
     const float v = to_f32<T>(x[i]) + to_f32<T>(res[i]);
-    s[i] = from_f32<T>(v);
+    if constexpr (PASS == 1) s[i] = from_f32<T>(v);
     return v;
   }
 };
@@ -111,12 +115,48 @@ struct EmbedSrc {
   }
 };
 
+// Sum a and b over the threads that share a row; every thread gets both.
+// On the block path every thread of the block has to call it, and a barrier
+// has to separate two calls.
+template <int BLOCK>
+__device__ __forceinline__ void row_allreduce(float& a, float& b, int tid) {
+  if constexpr (BLOCK == 0) {
+    a = wave_allreduce_sum(a);
+    b = wave_allreduce_sum(b);
+  } else {
+    constexpr int NWAVES = BLOCK / 64;
+    __shared__ float red[2][NWAVES];  // per-wave partials
+    a = wave_reduce_sum(a);
+    b = wave_reduce_sum(b);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = a; red[1][tid >> 6] = b; }
+    __syncthreads();
+    a = b = 0.f;
+    for (int w = 0; w < NWAVES; ++w) { a += red[0][w]; b += red[1][w]; }
+  }
+}
+
 // mean and 1/std of a row from its f32 sum and sum of squares.  The one
-// place that forms the variance (as sumsq/d - mean^2).
+// place that forms the variance.  sumsq/d - mean^2 loses log2(1 + mean^2/var)
+// bits to cancellation, so it stands only where that is at most one bit
+// (var > mean^2, which also makes it positive).  A row that fails this is
+// swept once more, out of the caches it was just read into: centred(m, s1,
+// m2) returns the row's sums of x - m and (x - m)^2.  s1 takes the rounding
+// of the first sum out of the mean, and m2/d, the spread about m, is at
+// least 0 and above the variance by (s1/d)^2, the square of a rounding
+// error.  Every thread of a row decides alike.
+template <typename F>
 __device__ __forceinline__ void row_stats(float sum, float sumsq, int d,
-                                          float eps, float& mean, float& rstd) {
+                                          float eps, float& mean, float& rstd,
+                                          F centred) {
   mean = sum / d;
-  rstd = rsqrtf(sumsq / d - mean * mean + eps);
+  float var = sumsq / d - mean * mean;
+  if (__builtin_expect(!(var > mean * mean), 0)) {
+    float s1 = 0.f, m2 = 0.f;
+    centred(mean, s1, m2);
+    mean += s1 / d;
+    var = m2 / d;
+  }
+  rstd = rsqrtf(var + eps);
 }
 
 template <typename T, typename Src, int BLOCK>
@@ -151,28 +191,28 @@ __global__ void ln_rows_kernel(Src src, const T* __restrict__ weight,
     sum += v;
     sumsq += v * v;
   }
+  row_allreduce<BLOCK>(sum, sumsq, tid);
 
   float mean, rstd;
-  if constexpr (WAVE) {
-    row_stats(wave_allreduce_sum(sum), wave_allreduce_sum(sumsq), d, eps,
-              mean, rstd);
-  } else {
-    constexpr int NWAVES = BLOCK / 64;
-    __shared__ float red[2][NWAVES];  // per-wave partials, then mean / rstd
-    const int lane = tid & 63, wave = tid >> 6;
-    sum = wave_reduce_sum(sum);
-    sumsq = wave_reduce_sum(sumsq);
-    if (lane == 0) { red[0][wave] = sum; red[1][wave] = sumsq; }
-    __syncthreads();
-    if (tid == 0) {
-      float s = 0.f, ss = 0.f;
-      for (int w = 0; w < NWAVES; ++w) { s += red[0][w]; ss += red[1][w]; }
-      row_stats(s, ss, d, eps, red[0][0], red[1][0]);
+  row_stats(sum, sumsq, d, eps, mean, rstd, [&](float m, float& s1, float& m2) {
+    for (int i = tid; i < dvec; i += STRIDE) {
+      T t[2][VEC];
+      src.template load<0>(i, t);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float c = src.template value<0>(t, j) - m;
+        s1 += c;
+        m2 += c * c;
+      }
     }
-    __syncthreads();
-    mean = red[0][0];
-    rstd = red[1][0];
-  }
+    for (int i = dvec * VEC + tid; i < d; i += STRIDE) {
+      float c = src.template at<0>(i) - m;
+      s1 += c;
+      m2 += c * c;
+    }
+    if constexpr (!WAVE) __syncthreads();
+    row_allreduce<BLOCK>(s1, m2, tid);
+  });
 
   for (int i = tid; i < dvec; i += STRIDE) {
     T t[2][VEC], tw[VEC], tb[VEC], ty[VEC];
